@@ -8,8 +8,11 @@ One "step" = one pass of the hot path over one batch of synthetic input resident
 Multi-GPU: streams are sharded over ranks (independent utterances, no data-path collective);
 one process per GPU, launched by torch.distributed.run; scaling is weak.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description), including
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and the launch
+configuration.  A plain run sets up, warms up, times the --steps steps and prints that line; --dump-outputs DIR also writes
+what the last timed step computed.  --full adds everything else the benchmark measures, after the timed steps:
   roofline     -- the dominant kernel (analysis bank) against the HBM roofline,
+  stages       -- per-stage times, the int16 entries, the adaptive chains, the node API, multi-GPU C5 partition,
   cpu_baseline -- the oracle (loop-faithful port of the reference's CPU path) on 1 host core.
 """
 import argparse
@@ -34,6 +37,22 @@ FUSED_ISA = {"kernel_source_sha256": "98cd814b2e72da2cb6b34596f639a17dff228c65bb
              "v_pk_fma_f32": 184, "v_pk_add_f32": 89, "v_pk_mul_f32": 23, "frames_per_wave": 4}
 TRAFFIC_JSON = "r06_pmc_traffic.json"      # profiles/: PMC traffic of the kernels below, with the launch size and kernel-source hash it holds for
 FS = 16000.0
+DUMP_ELEMS = 1 << 22       # --dump-outputs: values kept per array (two arrays at C0: 16 MB of PCM + 32 MB of subband frames)
+
+
+def dump_outputs(torch, d, arrays):
+    """Write each tensor of `arrays` as d/<name>.npy in float32 (complex as [..., 2] real / imaginary).  An array of more than
+    DUMP_ELEMS values is reduced to a fixed sample: DUMP_ELEMS flat indices drawn from numpy's default_rng(0), sorted, so two
+    runs with the same arguments write the same elements."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t.contiguous())
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def synth_pcm_device(torch, dev, S, N, L, delays, seed):
@@ -255,6 +274,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--staged", action="store_true",
                     help="time the staged chain (analysis -> HBM snapshots -> apply) instead of the fused kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the other stages and chains, the node API, the multi-GPU C5 "
+                         "partition and the CPU baseline (off: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (synthesized PCM, beamformed subband frames) as DIR/<name>.npy")
     args = ap.parse_args()
 
     # --gpus N is the contract: one rank per GPU.  Launched bare (no torch.distributed.run environment) with N > 1 the
@@ -321,7 +345,8 @@ def main():
     nblk = sfb.num_blocks(T)
     out = torch.empty((S, nblk * D), dtype=torch.float32, device=dev)
 
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)]
+    # per-step stage events feed the --full figures only
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(args.steps)] if args.full else [None] * args.steps
     fused = not args.staged
 
     def step(e=None):
@@ -347,14 +372,15 @@ def main():
     from bench_util import ClockPowerSampler
     # shader clock and package power while the timed steps run (sysfs, 2 ms period).  The sampler is set up and its thread started
     # BEFORE the warm-up: between the synchronisation that ends the warm-up and the first timed launch the GPU is idle, and its
-    # clock sags within a millisecond or two of idling
-    with ClockPowerSampler(torch, dev) as clk:
+    # clock sags within a millisecond or two of idling.  Only --full reports it.
+    import contextlib
+    with (ClockPowerSampler(torch, dev) if args.full else contextlib.nullcontext()) as clk:
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
         if dist: dist.barrier()
         torch.cuda.synchronize()
-        clk.begin()
+        if clk: clk.begin()
         t0 = time.perf_counter()
         for i in range(args.steps):
             step(ev[i])
@@ -368,12 +394,40 @@ def main():
     if dist:
         from distant_speech_recognition_amd import sharding
         elapsed = sharding.max_over_ranks(elapsed, dev)
-        # every rank's own rate (frames/s between the two barriers) and the world size the communicator itself reports
+        rccl_world = dist.get_world_size()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the --full stages below overwrite both buffers)
+        dump_outputs(torch, args.dump_outputs, {"pcm_out": out, "subband_out": Y[..., :T]})
+
+    res = None
+    if rank == 0:
+        value = S * T * world * args.steps / elapsed
+        res = {
+            "metric": "beamformed subband frames/sec, 64-mic 512-bin SubbandGSC",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "prewarm_steps": prewarm_steps,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "element": "complex64", "data": "synthetic",
+            "xRT": value / (FS / D),
+            "config": {"workload": "C0: %d-mic %d-bin SubbandGSC, analysis->GSC apply->synthesis (%s), m=4 r=1 (D=%d), "
+                                   "%d streams/GPU x %d frames/step" % (N, M, "fused analysis+apply" if fused else "staged", D, S, T),
+                       "streams_per_gpu": S, "frames_per_stream": T, "parallelism": "stream-sharded x%d" % world,
+                       "rccl_world": rccl_world, "dist_backend": (backend if dist else None),
+                       "y_row_stride_frames": int(Y.stride(1))},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    if dist:
+        # every rank's own rate (frames/s between the two barriers)
         mine = torch.tensor([per_rank[0]], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(v.item()) for v in allr]
-        rccl_world = dist.get_world_size()
 
     t_a = np.mean([e[0].elapsed_time(e[1]) for e in ev]) * 1e-3          # fused: analysis+apply kernel
     t_b = np.mean([e[1].elapsed_time(e[2]) for e in ev]) * 1e-3
@@ -447,10 +501,7 @@ def main():
         adaptive_wide = {"streams": S2, "frames_per_stream": T2, "ms": t2 * 1e3, "frames_per_s": S2 * T2 / t2, "xRT": S2 * T2 / t2 / (FS / D)}
         del pcm2, X2, Yc2, out2
 
-    res = None
     if rank == 0:
-        frames_per_step = S * T * world
-        value = frames_per_step * args.steps / elapsed
         b_ana = (4 * D + 8 * K) * N * S * T            # algorithmic bytes: analysis, per launch
         b_bf = 8 * K * (N + 1) * S * T                 # beamformer apply
         b_syn = (8 * K + 4 * D) * S * T
@@ -536,19 +587,8 @@ def main():
                     "unit": "GB/s", "frac": b_ana / t_ana / HBM_PEAK, "traffic": pmc_traffic("analysis512_kernel"),
                     "traffic_source": None, "bytes_per_launch": b_ana, "avg_launch_ms": t_ana * 1e3}
         roof["traffic_source"] = traffic_note.get("why")
-        res = {
-            "metric": "beamformed subband frames/sec, 64-mic 512-bin SubbandGSC",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "prewarm_steps": prewarm_steps,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "element": "complex64", "data": "synthetic",
-            "xRT": value / (FS / D),
-            "config": {"workload": "C0: %d-mic %d-bin SubbandGSC, analysis->GSC apply->synthesis (%s), m=4 r=1 (D=%d), "
-                                   "%d streams/GPU x %d frames/step" % (N, M, "fused analysis+apply" if fused else "staged", D, S, T),
-                       "streams_per_gpu": S, "frames_per_stream": T, "parallelism": "stream-sharded x%d" % world,
-                       "rccl_world": rccl_world, "dist_backend": (backend if dist else None),
-                       "per_rank_frames_per_s": per_rank,
-                       "y_row_stride_frames": int(Y.stride(1))},
+        res["config"]["per_rank_frames_per_s"] = per_rank
+        res.update({
             "roofline": roof,
             "stages": {
                 "fused_analysis_apply": ({"ms": t_a * 1e3, "frames_per_s": S * T / t_a,
@@ -589,7 +629,7 @@ def main():
                                                    "what": "the same chain, the analysis bank running 512-frame chunks ahead of the canceller on a second "
                                                            "HIP stream (engine.AdaptiveGSCChain); bit-identical output"},
             },
-        }
+        })
         if not args.no_cpu and world == 1:
             res["stages"]["node_api"] = node_api_stage(h, g, N, M, m, r, value)
             res["cpu_baseline"] = cpu_baseline(N, M, m, r, dct, args.cpu_frames)

@@ -14,9 +14,9 @@ mkdir -p $O/pmc_rw && cp -r $O/pmc_fetch $O/pmc_rw/ && cp -r $O/pmc_write $O/pmc
 python $R/profiles/make_traffic_json.py $O/pmc_rw $O/pmc_traffic.json 32 4096 > /dev/null 2>&1
 cp $O/pmc_traffic.json $R/profiles/r05_pmc_traffic.json          # bench.py below quotes it (same sources, same launch)
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --no-cpu > $O/bench_profiled.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --full --no-cpu > $O/bench_profiled.json 2> $O/prof.err
 DB=$(find $O/prof -name "*.db" | head -1)
 [ -n "$DB" ] && python $R/profiles/summarize_rocpd.py $DB $O/bench_kernel_stats.txt > /dev/null 2>&1
 cd $R

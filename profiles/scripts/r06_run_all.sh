@@ -15,10 +15,10 @@ mkdir -p $O/pmc_rw && cp -r $O/pmc_fetch $O/pmc_rw/ && cp -r $O/pmc_write $O/pmc
 python $R/profiles/make_traffic_json.py $O/pmc_rw $O/pmc_traffic.json 32 4096 > /dev/null 2>&1
 cp $O/pmc_traffic.json $R/profiles/r06_pmc_traffic.json          # bench.py below quotes it (same sources, same launch)
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err      # the driver's flags
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err      # the driver's flags
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --no-cpu > $O/bench_profiled.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $R/bench.py --full --no-cpu > $O/bench_profiled.json 2> $O/prof.err
 DB=$(find $O/prof -name "*.db" | head -1)
 [ -n "$DB" ] && python $R/profiles/summarize_rocpd.py $DB $O/bench_kernel_stats.txt > /dev/null 2>&1
 # the node API: HIP-API trace at two stream lengths (8 and 32 blocks of 1024 frames per pass): what is called per block

@@ -88,7 +88,7 @@ def test_bench_two_ranks_contract(dev):
     env = dict(os.environ, BTK_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--streams", "4", "--frames", "1024"]
+           "--streams", "4", "--frames", "1024", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -117,7 +117,7 @@ def test_bench_rccl_world_of_one_runs_the_multi_gpu_stage(dev):
     env.pop("BTK_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--streams", "4", "--frames", "1024", "--no-cpu"]
+           "--streams", "4", "--frames", "1024", "--no-cpu", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
