@@ -197,6 +197,8 @@ class FilterBank:
         if out.dtype != torch.complex64 or tuple(out.shape[:2]) != (S, self.K) or out.shape[2] < tcount:
             raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "Y must be complex64 [%d][%d][>=%d], got %s %s"
                                 % (S, self.K, tcount, out.dtype, tuple(out.shape)))
+        if tcount == 0:                           # a recording that ends inside the look-ahead: no frames, nothing to launch
+            return out
         nb = _lib.lib().btk_fb_analysis_bf_scratch_bytes(self._h, S, N, per_stream, tcount)
         # the weight-pair scratch is written by a kernel of THIS launch's stream: one buffer per (device, stream), so that a plan
         # shared by several streams (serving.BatchBeamformerPipeline next to a caller's own stream) never has two launches
