@@ -94,6 +94,12 @@ SIGNATURES = {
     "btk_csvdc_values": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "btk_mvdr_linpack_rule_scratch_bytes": (_l, [_i, _i]),
     "btk_mvdr_linpack_rule": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "btk_csvdc_full_scratch_bytes": (_l, [_i, _i, _i]),
+    "btk_csvdc_full": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btk_pinv_linpack_scratch_bytes": (_l, [_i, _i, _i]),
+    "btk_pinv_linpack": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "btk_mvdr_linpack_full_scratch_bytes": (_l, [_i, _i]),
+    "btk_mvdr_linpack_full": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "btk_mvdr_diffuse_model": (_i, [_vp, _i, _i, _f, _f, _vp, _vp]),
     "btk_mvdr_diagonal_loading": (_i, [_vp, _i, _i, _f, _vp]),
     "btk_mvdr_weights": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),

@@ -7,6 +7,7 @@
 // workgroup per matrix, float32 rounding for rounding (csrc/linpack_f32.h holds the body and explains why).  A bin the rule
 // sends to the identity gets w = d / (N d^H d) (and Lambda = d^H d); every other bin keeps the answer of the solver that ran
 // before.  Compiled with -ffp-contract=off (Makefile): a fused multiply-add anywhere would change INFO on borderline bins.
+// The second half of the file is csvdc with job = 11 -- U and V too -- and the pseudo-inverse assembled from them: svd_rule "linpack_full".
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "btk_internal.h"
@@ -64,16 +65,29 @@ __device__ __forceinline__ void rotg_dev(float& sa, float sb, float& c, float& s
 //    in registers and the next step's fresh s / e entries loaded one step ahead: no LDS round trip inside the dependent chain of
 //    srotg's four divisions and square root; stores are fire and forget (LDS executes a wavefront's accesses in order).
 // s, e: LDS, m entries each.  All 64 lanes call it with the same arguments; every lane returns INFO.
-__device__ int qr_iterate_wave(int m, float* s, float* e)
+// Sink: where the column operations on the singular vectors go (lpk::NoSink's interface plus full()).  NoSinkW (job = 0): nothing,
+// all of it compiled away.  LogSink (job = 11): a log in LDS the other wavefronts apply; when the log cannot take another pass the
+// walk returns QR_PAUSED with its position (m, iter; everything else is in s and e) and is called again with an empty log.
+constexpr int QR_PAUSED = -1;
+struct NoSinkW {
+  __device__ bool full() const { return false; }
+  __device__ void rot_v(int, int, float, float) const {}
+  __device__ void rot_u(int, int, float, float) const {}
+  __device__ void neg_v(int) const {}
+  __device__ void swap_v(int, int) const {}
+  __device__ void swap_u(int, int) const {}
+};
+template <class Sink>
+__device__ int qr_iterate_wave_t(int& m, int& iter, const int mm, float* s, float* e, const int n, const int p, Sink& sink)
 {
   const int lane = (int)(threadIdx.x & 63);
   const bool wr = lane == 0;
   const int maxit = 30;
-  const int mm = m;
-  int iter = 0, info = 0;
+  int info = 0;
   for (;;) {
     if (m == 0) break;
     if (maxit <= iter) { info = m; break; }
+    if (sink.full()) return QR_PAUSED;
     // l: the largest l in [1, m - 1] whose e(l) is negligible beside its two neighbours on the diagonal, else 0
     int l = 0;
     for (int base = m - 1; base >= 1; base -= 64) {
@@ -127,6 +141,7 @@ __device__ int qr_iterate_wave(int m, float* s, float* e)
         rotg_dev(t1, f, cs, sn);
         if (wr) s[k - 1] = t1;
         if (k != l) { f = -sn * e_k; if (wr) e[k - 2] = cs * e_k; }
+        sink.rot_v(k - 1, m - 1, cs, sn);
         s_k = s_n; e_k = e_n;
       }
     } else if (kase == 2) {                              // split at negligible s(l): k = l up to m
@@ -141,6 +156,7 @@ __device__ int qr_iterate_wave(int m, float* s, float* e)
         if (wr) s[k - 1] = t1;
         f = -sn * e_k;
         if (wr) e[k - 1] = cs * e_k;
+        sink.rot_u(k - 1, l - 2, cs, sn);
         s_k = s_n; e_k = e_n;
       }
     } else if (kase == 3) {                              // one shifted QR step
@@ -168,23 +184,27 @@ __device__ int qr_iterate_wave(int m, float* s, float* e)
         e_a = cs * e_a - sn * s_a;
         g = sn * s_b;
         s_b = cs * s_b;
+        sink.rot_v(k - 1, k, cs, sn);
         rotg_dev(f, g, cs, sn);
         if (wr) s[k - 1] = f;
         f = cs * e_a + sn * s_b;
         s_b = -sn * e_a + cs * s_b;
         g = sn * e_b;
         e_b = cs * e_b;
+        if (k < n) sink.rot_u(k - 1, k, cs, sn);
         s_a = s_b; e_a = e_b; s_b = s_n; e_b = e_n;
       }
       if (wr) { s[m - 1] = s_a; e[m - 1] = e_a; e[m - 2] = f; }
       iter = iter + 1;
     } else {                                             // convergence
       float a = s[l - 1];
-      if (a < 0.0f) { a = -a; if (wr) s[l - 1] = a; }
+      if (a < 0.0f) { a = -a; if (wr) s[l - 1] = a; sink.neg_v(l - 1); }
       while (l != mm) {
         const float nx = s[l];
         if (nx <= a) break;
         if (wr) { s[l - 1] = nx; s[l] = a; }
+        if (l < p) sink.swap_v(l - 1, l);
+        if (l < n) sink.swap_u(l - 1, l);
         l = l + 1;
       }
       iter = 0;
@@ -192,6 +212,12 @@ __device__ int qr_iterate_wave(int m, float* s, float* e)
     }
   }
   return info;
+}
+__device__ int qr_iterate_wave(int m, float* s, float* e)
+{
+  int iter = 0;
+  NoSinkW sink;
+  return qr_iterate_wave_t(m, iter, m, s, e, 0, 0, sink);
 }
 
 // lpk::nrm2 (scnrm2's scaled sum of squares, blas1_c.cc:1551-1660) by one wavefront, same roundings: a component either raises
@@ -505,6 +531,243 @@ int launch_values(const void* A, int K, int n, int p, float* s, float* e, int* i
   return BTK_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// job = 11: the singular VECTORS too, rotation for rotation (lpk::csvdc_full_prepare + the log below), and pseudoinverse()'s
+// A+ = V S^-1 U^H assembled from them in the source's order (beamformer.cc:262-280).
+//
+// One workgroup of four wavefronts per matrix; X (n x p, row-major) in the global scratch copy, U (n x n) and V (p x p) in global
+// memory as well (1.5 MB per 256 x 256 bin: L2 / HBM), column-major like the reference's once the iteration starts.  Every csrot /
+// cscal / cswap of the iteration acts on whole columns and treats each ROW on its own, and none of it feeds back into s, e or INFO:
+// the wavefront that walks the recurrence (qr_iterate_wave_t) only LOGS them -- (kind, column pair, cs, sn) in LDS -- and the three
+// other wavefronts apply the log in order, a thread per row, while the walk fills the other half of the log.
+constexpr int LF_THREADS = 256;
+constexpr int LF_MAX_N = 256;                      // n, p <= 256 (BASELINE C5); column indices take 12 bits of a log entry
+constexpr int LF_LOG_CAP = 896;                    // entries per half; one pass of the iteration logs at most 2 m + 1 <= 513.  With the
+                                                   // log in the row-sum tile's place a 256 x 256 bin asks for 38 KB: four bins per CU
+enum { LF_ROT_V = 0, LF_ROT_U = 1, LF_NEG_V = 2, LF_SWAP_V = 3, LF_SWAP_U = 4 };
+
+struct LogSink {
+  int* code; float2* csn; int count, need; bool wr;
+  __device__ bool full() const { return count + need > LF_LOG_CAP; }
+  __device__ void put(int kind, int a, int b, float cs, float sn)
+  {
+    if (wr) { code[count] = (kind << 24) | (a << 12) | b; csn[count] = make_float2(cs, sn); }
+    ++count;
+  }
+  __device__ void rot_v(int a, int b, float cs, float sn) { put(LF_ROT_V, a, b, cs, sn); }
+  __device__ void rot_u(int a, int b, float cs, float sn) { put(LF_ROT_U, a, b, cs, sn); }
+  __device__ void neg_v(int a) { put(LF_NEG_V, a, a, 0.f, 0.f); }
+  __device__ void swap_v(int a, int b) { put(LF_SWAP_V, a, b, 0.f, 0.f); }
+  __device__ void swap_u(int a, int b) { put(LF_SWAP_U, a, b, 0.f, 0.f); }
+};
+
+// One row of U (is_u) or V through `cnt` log entries, in order.  row: the row's element of column 0; columns are ld apart.  The
+// chases hand one column on from entry to entry ((k - 1, k) then (k, k + 1); the fixed column of a deflation): it stays in a
+// register (cc, cv) until an entry does not use it.
+__device__ void apply_log_row(lpk::cf* row, int ld, bool is_u, const int* code, const float2* csn, int cnt)
+{
+  int cc = -1;
+  lpk::cf cv = lpk::mk(0.f, 0.f);
+  for (int q = 0; q < cnt; ++q) {
+    const int c = code[q], kind = c >> 24, a = (c >> 12) & 0xfff, b = c & 0xfff;
+    const bool for_u = kind == LF_ROT_U || kind == LF_SWAP_U;
+    if (for_u != is_u) continue;
+    if (cc >= 0 && cc != a && cc != b) row[(long)cc * ld] = cv;
+    lpk::cf x = (a == cc) ? cv : row[(long)a * ld];
+    if (kind == LF_NEG_V) { lpk::neg_elem(x); cc = a; cv = x; continue; }
+    lpk::cf y = (b == cc) ? cv : row[(long)b * ld];
+    if (kind == LF_ROT_V || kind == LF_ROT_U) { const float2 r = csn[q]; lpk::rot_pair(x, y, r.x, r.y); }
+    else lpk::swap_pair(x, y);
+    row[(long)a * ld] = x;
+    cc = b; cv = y;
+  }
+  if (cc >= 0) row[(long)cc * ld] = cv;
+}
+
+__host__ __device__ inline size_t lf_lds(int n, int p)
+{
+  const size_t small = (lp_small_lds(n, p) + 15) & ~(size_t)15;
+  const size_t tile = sizeof(float2) * (size_t)n * (WgCtx::RT_J + 1), log = 2 * (size_t)LF_LOG_CAP * (sizeof(int) + sizeof(float2));
+  return small + (tile > log ? tile : log) + 16;               // (the tile serves the reduction, the log the iteration after it)
+}
+
+// A [K][n][p] row-major (not modified); xs: scratch [K][n][p]; U [K][n][n], V [K][p][p] column-major; s_out, e_out [K][m]; info_out
+// [K].  sinv_out (may be null) [K][p] complex and ok_out [K]: pseudoinverse()'s 1 / s[k] and return value (n >= p).  A DC bin
+// (skip_dc) is not decomposed: info = 0, ok = 0 (its weight is the all-ones vector, beamformer.cc:2369-2371).
+__global__ __launch_bounds__(LF_THREADS)
+void csvdc_full_kernel(const float2* __restrict__ A, int n, int p, float2* __restrict__ xs, float2* __restrict__ U,
+                       float2* __restrict__ V, float* __restrict__ s_out, float* __restrict__ e_out, int* __restrict__ info_out,
+                       float threshold, float2* __restrict__ sinv_out, int* __restrict__ ok_out, int skip_dc, int k_offset, int kper)
+{
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using lpk::cf;
+  const int k = blockIdx.x, tid = threadIdx.x, m = lp_m(n, p);
+  if (skip_dc && (kper > 0 ? (k % kper) == 0 : (k + k_offset) == 0)) {
+    if (tid == 0) { info_out[k] = 0; if (ok_out) ok_out[k] = 0; }
+    return;
+  }
+  cf* col = reinterpret_cast<cf*>(smem);
+  cf* ev = col + (n + 1);
+  cf* work = ev + (p + 1);
+  cf* sc = work + (n + 1);
+  cf* ec = sc + (n + p + 2);
+  cf* tt = ec + (n + p + 2);
+  float* s = reinterpret_cast<float*>(tt + 2);
+  float* e = s + m;
+  int* flag = reinterpret_cast<int*>(e + m);
+  const size_t small = (lp_small_lds(n, p) + 15) & ~(size_t)15;
+  cf* tile = reinterpret_cast<cf*>(smem + small);
+  float2* log_csn = reinterpret_cast<float2*>(tile);           // (shares the tile's place: lf_lds)
+  int* log_code = reinterpret_cast<int*>(log_csn + 2 * LF_LOG_CAP);
+  int* ctl = reinterpret_cast<int*>(smem + lf_lds(n, p) - 16);   // [0], [1]: entries in each half; [2]: the last chunk, -1 until known; [3]: INFO
+  cf* x = reinterpret_cast<cf*>(xs + (long)k * n * p);
+  cf* u = reinterpret_cast<cf*>(U + (long)k * n * n);
+  cf* v = reinterpret_cast<cf*>(V + (long)k * p * p);
+  const float2* Ak = A + (long)k * n * p;
+  for (int idx = tid; idx < n * p; idx += LF_THREADS) { const float2 a = Ak[idx]; x[idx] = lpk::mk(a.x, a.y); }
+  if (tid == 0) ctl[2] = -1;
+  __syncthreads();
+  lpk::Work w{col, ev, work, sc, ec, tt, flag};
+  WgCtx cx;
+  cx.qw = (int)(blockIdx.x % (LF_THREADS >> 6));
+  cx.info_slot = flag + 2;
+  cx.tile = tile;
+  lpk::csvdc_full_prepare(cx, x, p, n, p, w, s, e, u, v);
+  // the iteration: chunk t of the log is written by wavefront qw while the others apply chunk t - 1
+  const int wave = tid >> 6, lane = tid & 63;
+  const int na = LF_THREADS - 64, at = (wave < cx.qw ? wave : wave - 1) * 64 + lane;
+  int mcur = m, iter = 0;
+  bool done = false;
+  for (int t = 0;; ++t) {
+    const int h = t & 1;
+    if (wave == cx.qw) {
+      if (!done) {
+        LogSink sink{log_code + h * LF_LOG_CAP, log_csn + h * LF_LOG_CAP, 0, 2 * m + 2, lane == 0};
+        const int st = qr_iterate_wave_t(mcur, iter, m, s, e, n, p, sink);
+        if (lane == 0) ctl[h] = sink.count;
+        if (st != QR_PAUSED) { done = true; if (lane == 0) { ctl[2] = t; ctl[3] = st; } }
+      }
+    } else if (t > 0) {
+      const int cnt = ctl[h ^ 1];
+      if (cnt > 0)
+        for (int r = at; r < n + p; r += na) {
+          if (r < n) apply_log_row(u + r, n, true, log_code + (h ^ 1) * LF_LOG_CAP, log_csn + (h ^ 1) * LF_LOG_CAP, cnt);
+          else apply_log_row(v + (r - n), p, false, log_code + (h ^ 1) * LF_LOG_CAP, log_csn + (h ^ 1) * LF_LOG_CAP, cnt);
+        }
+    }
+    __syncthreads();
+    const int fin = ctl[2];
+    if (fin >= 0 && t > fin) break;
+  }
+  const int info = ctl[3];
+  if (tid == 0) info_out[k] = info;
+  for (int i = tid; i < m; i += LF_THREADS) { if (s_out) s_out[(long)k * m + i] = s[i]; if (e_out) e_out[(long)k * m + i] = e[i]; }
+  if (sinv_out) {                                              // beamformer.cc:262-270, every k on its own
+    int below = 0;
+    for (int i = tid; i < p; i += LF_THREADS) {
+      cf si;
+      below += lpk::pinv_sinv(1, s + i, threshold, &si);
+      sinv_out[(long)k * p + i] = make_float2(si.re, si.im);
+    }
+    const int nbelow = __syncthreads_count(below);
+    if (tid == 0) ok_out[k] = (info == 0 && nbelow == 0) ? 1 : 0;
+  }
+}
+
+struct GridCtx {
+  __device__ int tid() const { return (int)(blockIdx.y * blockDim.x + threadIdx.x); }
+  __device__ int nthreads() const { return (int)(gridDim.y * blockDim.x); }
+};
+// lpk::pinv_assemble, a thread per element of invA [K][N][M]; only_ok: a bin whose inverse both callers discard is not assembled
+__global__ __launch_bounds__(256)
+void pinv_assemble_kernel(const float2* __restrict__ U, const float2* __restrict__ V, const float2* __restrict__ sinv, int M, int N,
+                          float2* __restrict__ invA, const int* __restrict__ ok, int only_ok)
+{
+  __shared__ lpk::cf sv[LF_MAX_N];
+  const int k = blockIdx.x;
+  if (only_ok && !ok[k]) return;
+  for (int i = threadIdx.x; i < N; i += blockDim.x) { const float2 z = sinv[(long)k * N + i]; sv[i] = lpk::mk(z.x, z.y); }
+  __syncthreads();
+  GridCtx cx;
+  lpk::pinv_assemble(cx, M, N, reinterpret_cast<const lpk::cf*>(U + (long)k * M * M), reinterpret_cast<const lpk::cf*>(V + (long)k * N * N), sv,
+                     reinterpret_cast<lpk::cf*>(invA + (long)k * N * M));
+}
+
+// calc_mvdr_weights after pseudoinverse() (beamformer.cc:2381-2396) / calcLambda (postfilter.cc:982-995), float64 like gsl's zgemv
+// (ConjTrans: tmpH_j = sum_i conj(inv(i, j)) d_i, i ascending) and zdotc on the float32-valued inverse -- or on the identity where
+// pseudoinverse() returned false --, rounded once to complex64.  One workgroup per bin; the DC bin of a design gets the all-ones weight.
+__global__ __launch_bounds__(256)
+void mvdr_full_weights_kernel(const float2* __restrict__ invA, const int* __restrict__ ok, const int* __restrict__ info,
+                              const float2* __restrict__ Dq, float2* __restrict__ W, float2* __restrict__ lambda_out, int N,
+                              int skip_dc, int k_offset, int kper, int* __restrict__ counts)
+{
+  __shared__ double2 th[LF_MAX_N];
+  __shared__ double2 lam;
+  const int k = blockIdx.x, tid = threadIdx.x;
+  if (skip_dc && (kper > 0 ? (k % kper) == 0 : (k + k_offset) == 0)) {
+    if (W) for (int c = tid; c < N; c += blockDim.x) W[(long)k * N + c] = make_float2(1.f, 0.f);
+    return;
+  }
+  const float2* d = Dq + (long)k * N;
+  const bool good = ok[k] != 0;
+  for (int j = tid; j < N; j += blockDim.x) {
+    double2 acc = make_double2((double)d[j].x, (double)d[j].y);
+    if (good) {
+      const float2* a = invA + (long)k * N * N + j;
+      acc = make_double2(0.0, 0.0);
+      for (int i = 0; i < N; ++i) {
+        const double ar = (double)a[(long)i * N].x, ai = -(double)a[(long)i * N].y, dr = (double)d[i].x, di = (double)d[i].y;
+        acc.x += ar * dr - ai * di;
+        acc.y += ar * di + ai * dr;
+      }
+    }
+    th[j] = acc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double lr = 0.0, li = 0.0;
+    for (int j = 0; j < N; ++j) {
+      const double tr = th[j].x, ti = -th[j].y, dr = (double)d[j].x, di = (double)d[j].y;
+      lr += tr * dr - ti * di;
+      li += tr * di + ti * dr;
+    }
+    lam = make_double2(lr, li);
+    if (lambda_out) lambda_out[k] = make_float2((float)lr, (float)li);
+    if (counts && !good) atomicAdd(&counts[info[k] != 0 ? 0 : 1], 1);
+  }
+  __syncthreads();
+  if (W) {
+    const double nr = lam.x * (double)N, ni = lam.y * (double)N, den = nr * nr + ni * ni;
+    for (int j = tid; j < N; j += blockDim.x)
+      W[(long)k * N + j] = make_float2((float)((th[j].x * nr + th[j].y * ni) / den), (float)((th[j].y * nr - th[j].x * ni) / den));
+  }
+}
+
+int launch_full(const char* who, const void* A, int K, int n, int p, float* s, float* e, void* U, void* V, int* info, void* xs,
+                float threshold, void* sinv, int* ok, int skip_dc, int k_offset, int kper, hipStream_t st)
+{
+  if (K < 1 || n < 1 || p < 1 || n > LF_MAX_N || p > LF_MAX_N)
+    return btk_set_error(BTK_ERR_DIMENSION, "%s: K=%d matrices of %d x %d: sizes from 1 to %d are supported", who, K, n, p, LF_MAX_N);
+  const size_t lds = lf_lds(n, p);
+  if (lds > 64 * 1024)
+    BTK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(csvdc_full_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(csvdc_full_kernel, dim3((unsigned)K), dim3(LF_THREADS), lds, st, static_cast<const float2*>(A), n, p,
+                     static_cast<float2*>(xs), static_cast<float2*>(U), static_cast<float2*>(V), s, e, info, threshold,
+                     static_cast<float2*>(sinv), ok, skip_dc, k_offset, kper);
+  BTK_HIP_CHECK(hipGetLastError());
+  return BTK_OK;
+}
+inline long al256(long b) { return (b + 255) & ~255L; }
+int launch_assemble(const void* U, const void* V, const void* sinv, int K, int M, int N, void* invA, const int* ok, int only_ok, hipStream_t st)
+{
+  const unsigned by = (unsigned)(((long)M * N + 255) / 256);
+  hipLaunchKernelGGL(pinv_assemble_kernel, dim3((unsigned)K, by), dim3(256), 0, st, static_cast<const float2*>(U), static_cast<const float2*>(V),
+                     static_cast<const float2*>(sinv), M, N, static_cast<float2*>(invA), ok, only_ok);
+  BTK_HIP_CHECK(hipGetLastError());
+  return BTK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -540,6 +803,75 @@ int btk_mvdr_linpack_rule(const void* R, const void* wq, void* W, void* lambda, 
   if (rc != BTK_OK) return rc;
   hipLaunchKernelGGL(identity_rule_kernel, dim3((unsigned)K), dim3(64), 0, st, rule, info, static_cast<const float2*>(wq),
                      static_cast<float2*>(W), static_cast<float2*>(lambda), N, fail_flags, counts);
+  BTK_HIP_CHECK(hipGetLastError());
+  return BTK_OK;
+}
+
+long btk_csvdc_full_scratch_bytes(int K, int n, int p)
+{
+  if (K < 1 || n < 1 || p < 1) return 0;
+  return al256((long)sizeof(float2) * K * n * p);
+}
+
+int btk_csvdc_full(const void* A, int K, int n, int p, float* s, float* e, void* U, void* V, int* info, void* scratch, void* stream)
+{
+  if (!A || !U || !V || !info || !scratch) return btk_set_error(BTK_ERR_PARAMETER, "btk_csvdc_full: null argument");
+  return launch_full("btk_csvdc_full", A, K, n, p, s, e, U, V, info, scratch, 0.f, nullptr, nullptr, 0, 0, 0, as_stream(stream));
+}
+
+// scratch of the pseudo-inverse: X [K][M][N], U [K][M][M], V [K][N][N], sinv [K][N], s [K][N] in this order
+long btk_pinv_linpack_scratch_bytes(int K, int M, int N)
+{
+  if (K < 1 || M < 1 || N < 1) return 0;
+  const long c = (long)sizeof(float2);
+  return al256(c * K * M * N) + al256(c * K * M * M) + al256(c * K * N * N) + al256(c * K * N) + al256((long)sizeof(float) * K * N);
+}
+
+int btk_pinv_linpack(const void* A, int K, int M, int N, float threshold, void* invA, int* ok, int* info, void* scratch, void* stream)
+{
+  if (!A || !invA || !ok || !info || !scratch) return btk_set_error(BTK_ERR_PARAMETER, "btk_pinv_linpack: null argument");
+  if (M < N) return btk_set_error(BTK_ERR_DIMENSION, "btk_pinv_linpack: pseudoinverse() is defined for M >= N, got %d x %d", M, N);
+  if (K < 1 || N < 1 || M > LF_MAX_N) return btk_set_error(BTK_ERR_DIMENSION, "btk_pinv_linpack: K=%d matrices of %d x %d: sizes from 1 to %d are supported", K, M, N, LF_MAX_N);
+  hipStream_t st = as_stream(stream);
+  const long c = (long)sizeof(float2);
+  char* xs = static_cast<char*>(scratch);
+  char* U = xs + al256(c * K * M * N);
+  char* V = U + al256(c * K * M * M);
+  char* sinv = V + al256(c * K * N * N);
+  float* s = reinterpret_cast<float*>(sinv + al256(c * K * N));
+  const int rc = launch_full("btk_pinv_linpack", A, K, M, N, s, nullptr, U, V, info, xs, threshold, sinv, ok, 0, 0, 0, st);
+  if (rc != BTK_OK) return rc;
+  return launch_assemble(U, V, sinv, K, M, N, invA, ok, 0, st);
+}
+
+long btk_mvdr_linpack_full_scratch_bytes(int K, int N)
+{
+  if (K < 1 || N < 1) return 0;
+  return btk_pinv_linpack_scratch_bytes(K, N, N) + al256((long)sizeof(float2) * K * N * N) + al256((long)sizeof(int) * 2 * K);
+}
+
+int btk_mvdr_linpack_full(const void* R, const void* wq, void* W, void* lambda, int K, int N, int first_bin, int kper, int skip_dc,
+                          float threshold, int* counts, void* scratch, void* stream)
+{
+  if (!R || !wq || !scratch || (!W && !lambda)) return btk_set_error(BTK_ERR_PARAMETER, "btk_mvdr_linpack_full: null argument");
+  if (K < 1 || N < 1 || N > LF_MAX_N || first_bin < 0 || kper < 0)
+    return btk_set_error(BTK_ERR_DIMENSION, "btk_mvdr_linpack_full: K=%d bins of %d channels: 1 to %d channels are supported", K, N, LF_MAX_N);
+  hipStream_t st = as_stream(stream);
+  const long c = (long)sizeof(float2);
+  char* xs = static_cast<char*>(scratch);
+  char* U = xs + al256(c * K * N * N);
+  char* V = U + al256(c * K * N * N);
+  char* sinv = V + al256(c * K * N * N);
+  float* s = reinterpret_cast<float*>(sinv + al256(c * K * N));
+  char* inv = static_cast<char*>(scratch) + btk_pinv_linpack_scratch_bytes(K, N, N);
+  int* ok = reinterpret_cast<int*>(inv + al256(c * K * N * N));
+  int* info = ok + K;
+  int rc = launch_full("btk_mvdr_linpack_full", R, K, N, N, s, nullptr, U, V, info, xs, threshold, sinv, ok, skip_dc, first_bin, kper, st);
+  if (rc != BTK_OK) return rc;
+  rc = launch_assemble(U, V, sinv, K, N, N, inv, ok, 1, st);
+  if (rc != BTK_OK) return rc;
+  hipLaunchKernelGGL(mvdr_full_weights_kernel, dim3((unsigned)K), dim3(256), 0, st, reinterpret_cast<const float2*>(inv), ok, info,
+                     static_cast<const float2*>(wq), static_cast<float2*>(W), static_cast<float2*>(lambda), N, skip_dc, first_bin, kper, counts);
   BTK_HIP_CHECK(hipGetLastError());
   return BTK_OK;
 }

@@ -824,6 +824,9 @@ class CoherencePostFilterState:
             raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "svd_rule must be one of %s, got %r" % (SVD_RULES, rule))
         R, d = R.contiguous(), d.contiguous()
         self.lam = torch.empty((K,), dtype=torch.complex64, device=R.device)
+        if rule == "linpack_full":          # d^H A+ d from the reference's own inverse, d^H d where pseudoinverse() returns false
+            counts = _linpack_full(R, d, None, self.lam, K, N, 0, 0, 0, min_sv)
+            return int(counts.sum().item())
         fb = torch.zeros(1, dtype=torch.int32, device=R.device)
         sb = _lib.lib().btk_mvdr_scratch_bytes(K, N)
         scratch = torch.empty((sb,), dtype=torch.uint8, device=R.device) if sb else None
@@ -993,7 +996,7 @@ def mvdr_diagonal_loading(R, weight):
     return R
 
 
-SVD_RULES = ("linpack", "exact")
+SVD_RULES = ("linpack", "exact", "linpack_full")
 
 
 def svd_rule_default():
@@ -1001,7 +1004,9 @@ def svd_rule_default():
     "linpack" (default) takes the decision of the reference's float32 csvdc, rounding for rounding -- INFO != 0 or a singular
     value under the threshold -- so a design matches the reference bin for bin (on BASELINE config C5 that is delay-and-sum on
     about half the spectrum); "exact" solves every positive definite bin and uses the identity only where a singular value is
-    really below the threshold.  BTK_MVDR_SVD_RULE overrides the default."""
+    really below the threshold; "linpack_full" computes the reference's weights themselves: csvdc with its singular vectors,
+    the pseudo-inverse A+ = V S^-1 U^H assembled in the source's order and the float64 weight step on it, the identity where
+    pseudoinverse() returns false (no Cholesky solve, no fall-back; up to 256 channels).  BTK_MVDR_SVD_RULE overrides the default."""
     rule = os.environ.get("BTK_MVDR_SVD_RULE", "linpack")
     if rule not in SVD_RULES:
         raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "BTK_MVDR_SVD_RULE must be one of %s, got %r" % (SVD_RULES, rule))
@@ -1035,6 +1040,51 @@ def _linpack_rule(R, wq, W, lam, KS, N, first_bin, kper, skip_dc, threshold, fla
     return counts
 
 
+def csvdc_full(A):
+    """LINPACK's float32 csvdc with job = 11 (matrix/linpack_c.cc:9516) for a batch: A complex64 [K][n][p] (cuda) ->
+    (s float32 [K][m], e float32 [K][m], U complex64 [K][n][n], V complex64 [K][p][p], info int32 [K]), m = min(n + 1, p);
+    U[k, i, j] / V[k, i, j] are the reference's u[i + j * ldu] / v[i + j * ldv] (the tensors are views of column-major storage).
+    Bit-identical to the reference's compiled routine; n, p <= 256."""
+    _check(A, "A", torch.complex64, 3)
+    K, n, p = A.shape
+    m = min(n + 1, p)
+    s = torch.zeros((K, m), dtype=torch.float32, device=A.device)
+    e = torch.zeros((K, m), dtype=torch.float32, device=A.device)
+    U = torch.zeros((K, n, n), dtype=torch.complex64, device=A.device)
+    V = torch.zeros((K, p, p), dtype=torch.complex64, device=A.device)
+    info = torch.zeros((K,), dtype=torch.int32, device=A.device)
+    if K > 0:
+        scratch = torch.empty((max(_lib.lib().btk_csvdc_full_scratch_bytes(K, n, p), 16),), dtype=torch.uint8, device=A.device)
+        check(_lib.lib().btk_csvdc_full(_ptr(A), K, n, p, _ptr(s), _ptr(e), _ptr(U), _ptr(V), _ptr(info), _ptr(scratch), _stream()))
+    return s, e, U.transpose(1, 2), V.transpose(1, 2), info
+
+
+def pinv_linpack(A, threshold=1.0e-8):
+    """pseudoinverse() (beamformer/beamformer.cc:232-289) for a batch on the device, the reference's own float32 arithmetic:
+    A complex64 [K][M][N] (cuda), M >= N -> (invA complex64 [K][N][M], ok bool [K] -- its return value --, info int32 [K])."""
+    _check(A, "A", torch.complex64, 3)
+    K, M, N = A.shape
+    invA = torch.zeros((K, N, M), dtype=torch.complex64, device=A.device)
+    ok = torch.zeros((K,), dtype=torch.int32, device=A.device)
+    info = torch.zeros((K,), dtype=torch.int32, device=A.device)
+    if M < N:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "pinv_linpack: pseudoinverse() is defined for M >= N, got %d x %d" % (M, N))
+    if K > 0:
+        scratch = torch.empty((max(_lib.lib().btk_pinv_linpack_scratch_bytes(K, M, N), 16),), dtype=torch.uint8, device=A.device)
+        check(_lib.lib().btk_pinv_linpack(_ptr(A), K, M, N, float(threshold), _ptr(invA), _ptr(ok), _ptr(info), _ptr(scratch), _stream()))
+    return invA, ok != 0, info
+
+
+def _linpack_full(R, wq, W, lam, KS, N, first_bin, kper, skip_dc, threshold):
+    """btk_mvdr_linpack_full on the current stream; returns the device counters [INFO != 0, singular value < threshold]."""
+    counts = torch.zeros(2, dtype=torch.int32, device=R.device)
+    scratch = torch.empty((_lib.lib().btk_mvdr_linpack_full_scratch_bytes(KS, N),), dtype=torch.uint8, device=R.device)
+    check(_lib.lib().btk_mvdr_linpack_full(_ptr(R), _ptr(wq), None if W is None else _ptr(W), None if lam is None else _ptr(lam),
+                                           KS, N, int(first_bin), int(kper), int(skip_dc), float(threshold), _ptr(counts),
+                                           _ptr(scratch), _stream()))
+    return counts
+
+
 def mvdr_weights(R, wq, threshold=1.0e-8, first_bin=0, svd_rule=None):
     """R complex64 [K][N][N], wq complex64 [K][N] (cuda) -> (W [K][N], number of bins that ended with the identity).
     first_bin: global index of row 0 when R / wq are one rank's bin range (only global bin 0 gets the all-ones weight).
@@ -1043,7 +1093,8 @@ def mvdr_weights(R, wq, threshold=1.0e-8, first_bin=0, svd_rule=None):
     calc_mvdr_weights (beamformer.cc:253-270, 2379-2396); every other bin keeps the Cholesky solution.  Bins whose Cholesky
     factorisation stops (R_k not positive definite) and that the rule did not already decide are re-solved through the
     pseudo-inverse (btk_mvdr_pinv_fallback).  mvdr_weights.last_counts = (INFO != 0, converged but under the threshold,
-    identity from the fall-back) of the last call.
+    identity from the fall-back) of the last call.  With "linpack_full" every bin takes the reference's own float32 SVD
+    pseudo-inverse (or the identity where pseudoinverse() returns false) and the float64 weight step: no Cholesky, third count 0.
     S streams at once: R [S][K][N][N], wq [S][K][N] -> W [S][K][N] (btk_mvdr_weights_streams: one launch, every stream's bin 0
     gets the all-ones weight; first_bin must be 0)."""
     rule = svd_rule_default() if svd_rule is None else svd_rule
@@ -1067,7 +1118,13 @@ def mvdr_weights(R, wq, threshold=1.0e-8, first_bin=0, svd_rule=None):
     flags = torch.zeros(max(KS, 1), dtype=torch.int32, device=R.device)
     nident = 0
     mvdr_weights.last_counts = (0, 0, 0)
-    if KS > 0:
+    if KS > 0 and rule == "linpack_full":
+        R, wq = R.contiguous(), wq.contiguous()
+        counts = _linpack_full(R, wq, W, None, KS, N, first_bin, K if batched else 0, 1, threshold)
+        c0, c1 = (int(v) for v in counts.tolist())
+        nident = c0 + c1
+        mvdr_weights.last_counts = (c0, c1, 0)
+    elif KS > 0:
         sb = _lib.lib().btk_mvdr_scratch_bytes(KS, N)
         scratch = torch.empty((sb,), dtype=torch.uint8, device=R.device) if sb else None
         sp = None if scratch is None else _ptr(scratch)

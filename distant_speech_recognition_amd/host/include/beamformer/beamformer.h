@@ -361,7 +361,8 @@ class SubbandMVDR : public SubbandDS {
   int identity_fallbacks() const { return fallbacks_; }
   // Which bins take the identity in place of inv(R_k) (reference beamformer.cc:253-270, 2379-2384): "linpack" (default; the
   // environment variable BTK_MVDR_SVD_RULE overrides) = exactly where the reference's float32 csvdc reports INFO != 0 or
-  // leaves a singular value under the threshold; "exact" = only where a singular value really is under the threshold.
+  // leaves a singular value under the threshold; "exact" = only where a singular value really is under the threshold;
+  // "linpack_full" = the reference's weights themselves: its float32 SVD pseudo-inverse on every bin (btk_mvdr_linpack_full, <= 256 channels).
   void set_svd_rule(const String& rule);
   const String& svd_rule() const { return svd_rule_; }
   int csvdc_not_converged() const { return csvdc_not_converged_; }    // bins of the last design with INFO != 0

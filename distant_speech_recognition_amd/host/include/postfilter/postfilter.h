@@ -94,7 +94,7 @@ class McCowanPostFilter : public ZelinskiPostFilter {
   void divideAllNonDiagonalElements(float mu) { divide_all_nondiagonal_elements(mu); }
   void divideNonDiagonalElements(unsigned fbinX, float mu) { divide_nondiagonal_elements(fbinX, mu); }
   // Lefkimmiatis: which bins take the identity in place of pinv(R_k) when Lambda is formed -- "linpack" (default; the
-  // environment variable BTK_MVDR_SVD_RULE overrides) or "exact", as SubbandMVDR::set_svd_rule (beamformer/beamformer.h)
+  // environment variable BTK_MVDR_SVD_RULE overrides), "exact" or "linpack_full", as SubbandMVDR::set_svd_rule (beamformer/beamformer.h)
   void set_svd_rule(const String& rule);
   const String& svd_rule() const { return svd_rule_; }
  protected:

@@ -2054,18 +2054,19 @@ void SubbandGSC::effective_weights_all_bins(std::vector<float>& w)
 }
 
 // ================================================================================ SubbandMVDR
-// "linpack" | "exact": see SubbandMVDR::set_svd_rule (beamformer.h); BTK_MVDR_SVD_RULE overrides the default "linpack"
+// "linpack" | "exact" | "linpack_full": see SubbandMVDR::set_svd_rule (beamformer.h); BTK_MVDR_SVD_RULE overrides the default "linpack"
+static bool known_svd_rule(const String& rule) { return rule == "linpack" || rule == "exact" || rule == "linpack_full"; }
 static String default_svd_rule()
 {
   const char* e = getenv("BTK_MVDR_SVD_RULE");
   if (!e || !*e) return "linpack";
-  if (strcmp(e, "linpack") && strcmp(e, "exact")) throw jparameter_error("BTK_MVDR_SVD_RULE must be linpack or exact, got %s\n", e);
+  if (!known_svd_rule(e)) throw jparameter_error("BTK_MVDR_SVD_RULE must be linpack, exact or linpack_full, got %s\n", e);
   return e;
 }
 
 void SubbandMVDR::set_svd_rule(const String& rule)
 {
-  if (rule != "linpack" && rule != "exact") throw jparameter_error("svd rule must be linpack or exact, got %s\n", rule.c_str());
+  if (!known_svd_rule(rule)) throw jparameter_error("svd rule must be linpack, exact or linpack_full, got %s\n", rule.c_str());
   svd_rule_ = rule;
 }
 
@@ -2172,6 +2173,26 @@ bool SubbandMVDR::calc_mvdr_weights(float, float dThreshold, bool)
   alignment_vector(true, d);
   void* dD = dev_alloc(sizeof(float) * d.size());
   void* dW = dev_alloc(sizeof(float) * d.size());
+  if (svd_rule_ == "linpack_full") {
+    // the reference's own float32 SVD pseudo-inverse and float64 weight step on every bin (beamformer.cc:232-289, 2372-2397):
+    // no Cholesky solve, no fall-back; the identity where pseudoinverse() returns false
+    int counts[2] = {0, 0};
+    void* dcnt = dev_alloc(sizeof(int) * 2);
+    void* fs = dev_alloc((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
+    h2d(dD, d.data(), sizeof(float) * d.size());
+    dev_zero_async(dcnt, sizeof(int) * 2);
+    check_abi(btk_mvdr_linpack_full(dR_, dD, dW, NULL, (int)K, (int)N, 0, 0, 1, dThreshold, (int*)dcnt, fs, nstream()));
+    nsync();
+    d2h(counts, dcnt, sizeof(counts));
+    csvdc_not_converged_ = counts[0];
+    fallbacks_ = counts[0] + counts[1];
+    wmvdr_.resize(d.size());
+    d2h(wmvdr_.data(), dW, sizeof(float) * wmvdr_.size());
+    dev_free(dD); dev_free(dW); dev_free(dcnt); dev_free(fs);
+    have_mvdr_ = true;
+    weights_version_++;
+    return true;
+  }
   void* dfb = dev_alloc(sizeof(int));
   const long sbytes = btk_mvdr_scratch_bytes((int)K, (int)N);                   // (only the panel solver copies R)
   void* scratch = sbytes ? dev_alloc((size_t)sbytes) : NULL;
@@ -2667,7 +2688,7 @@ McCowanPostFilter::McCowanPostFilter(VectorComplexFeatureStreamPtr& output, unsi
 
 void McCowanPostFilter::set_svd_rule(const String& rule)
 {
-  if (rule != "linpack" && rule != "exact") throw jparameter_error("svd rule must be linpack or exact, got %s\n", rule.c_str());
+  if (!known_svd_rule(rule)) throw jparameter_error("svd rule must be linpack, exact or linpack_full, got %s\n", rule.c_str());
   if (rule != svd_rule_) { svd_rule_ = rule; prepared_ = false; }
 }
 
@@ -2827,6 +2848,16 @@ void McCowanPostFilter::compute_(long from_frame)
       // Lambda = d^H pinv(R) d of every bin (:967-995) depends on the coherence matrix, the look direction and the SVD rule only:
       // designed once and kept until one of them changes (the csvdc rule alone takes ~0.1 s at 256 channels -- per block it
       // would dominate a stream)
+      if (svd_rule_ == "linpack_full" && (!lam_valid_ || lam_version_ != bf->weights_version() || lam_rule_ != svd_rule_)) {
+        void* dLam = dLamb_.ensure(sizeof(float) * 2 * K);
+        {                                                  // d^H A+ d from the reference's own inverse, every bin incl. 0 (:967-995)
+          void* fs = dev_alloc((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
+          check_abi(btk_mvdr_linpack_full(dR_, dD, NULL, dLam, (int)K, (int)N, 0, 0, 0, (float)minSV_, NULL, fs, nstream()));
+          nsync();
+          dev_free(fs);
+          lam_valid_ = true; lam_version_ = bf->weights_version(); lam_rule_ = svd_rule_;
+        }
+      }
       if (!lam_valid_ || lam_version_ != bf->weights_version() || lam_rule_ != svd_rule_) {
         void* dLam = dLamb_.ensure(sizeof(float) * 2 * K);
         void* dFb = dev_alloc(sizeof(int));

@@ -379,6 +379,30 @@ int  btk_csvdc_values(const void* A, int K, int n, int p, float* s, float* e, in
 long btk_mvdr_linpack_rule_scratch_bytes(int K, int N);
 int  btk_mvdr_linpack_rule(const void* R, const void* wq, void* W, void* lambda, int K, int N, int first_bin, int kper,
                            int skip_dc, float threshold, int* fail_flags, int* counts, void* scratch, void* stream);
+/* ---- The reference's float32 SVD pseudo-inverse itself: csvdc with job = 11 and A+ = V S^-1 U^H -----------------------------
+ * The third MVDR rule ("linpack_full"): not only pseudoinverse()'s decision but its matrix.  csvdc's U and V are produced rotation
+ * for rotation (matrix/linpack_c.cc:9727-9733, 9777-9783, 9812-9882, 9899-9920 and the csrot / cscal / cswap of the iteration,
+ * :10052-10055, 10074-10077, 10133-10148, 10164-10167, 10183-10191), the inverse is assembled from them in the source's order
+ * (beamformer/beamformer.cc:262-280) and the weights follow in float64 (:2386-2396).  Sizes: 1 <= n, p <= 256.
+ * btk_csvdc_full: K matrices A [dev] complex64 [K][n][p] row-major (not modified) -> s, e [dev] float32 [K][min(n + 1, p)] (either
+ *   may be NULL), U [dev] complex64 [K][n][n] and V [K][p][p], each matrix COLUMN-major like the reference's u, v (element (i, k) at
+ *   [i + k * n]), info [dev] int32 [K]; scratch [dev] btk_csvdc_full_scratch_bytes(K, n, p) bytes.  Bit-identical to the
+ *   reference's compiled csvdc (tests/test_gpu_linpack_full.py).
+ * btk_pinv_linpack: pseudoinverse() (beamformer.cc:232-289) of K matrices A [K][M][N], M >= N: invA [dev] complex64 [K][N][M]
+ *   row-major, computed for every matrix; ok [dev] int32 [K]: its return value (INFO == 0 and no singular value under the
+ *   threshold); info [dev] int32 [K]; scratch [dev] btk_pinv_linpack_scratch_bytes(K, M, N) bytes.
+ * btk_mvdr_linpack_full: calc_mvdr_weights (beamformer.cc:2372-2397) / calcLambda (postfilter/postfilter.cc:967-995) for K bins:
+ *   R [K][N][N], wq [K][N] -> W [K][N] (may be NULL) and lambda [K] = d^H A+ d (may be NULL), for EVERY bin: from the reference's
+ *   inverse where pseudoinverse() returns true, from the identity where not.  first_bin, kper, skip_dc as btk_mvdr_linpack_rule
+ *   (a skipped DC bin gets the all-ones weight, :2369-2371, and no lambda); counts [dev int[2]] (may be NULL) as there;
+ *   scratch [dev] btk_mvdr_linpack_full_scratch_bytes(K, N) bytes.  All on `stream`, no allocation, no synchronisation.      */
+long btk_csvdc_full_scratch_bytes(int K, int n, int p);
+int  btk_csvdc_full(const void* A, int K, int n, int p, float* s, float* e, void* U, void* V, int* info, void* scratch, void* stream);
+long btk_pinv_linpack_scratch_bytes(int K, int M, int N);
+int  btk_pinv_linpack(const void* A, int K, int M, int N, float threshold, void* invA, int* ok, int* info, void* scratch, void* stream);
+long btk_mvdr_linpack_full_scratch_bytes(int K, int N);
+int  btk_mvdr_linpack_full(const void* R, const void* wq, void* W, void* lambda, int K, int N, int first_bin, int kper, int skip_dc,
+                           float threshold, int* counts, void* scratch, void* stream);
 /* The same solve for a bin SHARD [first_bin, first_bin + K) of a bin-sharded run: only global bin 0 gets the
  * all-ones weight of calc_mvdr_weights (beamformer.cc:2369-2371).                                                    */
 int  btk_mvdr_weights_shard(const void* R, const void* wq, void* W, int K, int N, int first_bin, float threshold,
