@@ -127,6 +127,13 @@ SIGNATURES = {
     "btk_weights_blocking_matrix": (_i, [_vp, _i, _i, _vp]),
     "btk_weights_sidelobe": (_i, [_vp, _vp, _i, _i, _vp]),
     "btk_weights_gsc_effective": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "btk_srp_grid": (_i, [_f, _f, _f, C.POINTER(_i), _vp]),
+    "btk_srp_delays": (_i, [_i, _vp, _d, _vp]),
+    "btk_srp_table": (_i, [_i, _i, _f, _vp, _i, _vp, _i, _i, _vp]),
+    "btk_srp_packed_elems": (_l, [_i, _i, _i]),
+    "btk_srp_pack_table": (_i, [_vp, _i, _i, _i, _vp]),
+    "btk_srp_power": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _i, _i, _i, _vp]),
+    "btk_srp_select": (_i, [_vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _l, _vp]),
 }
 
 

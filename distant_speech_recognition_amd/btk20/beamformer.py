@@ -3,6 +3,8 @@
 from ..btk20cpp import (  # noqa: F401
     SSPEED, SnapShotArrayPtr, SpectralMatrixArrayPtr, SubbandDSPtr, SubbandGSCPtr, SubbandGSCRLSPtr, SubbandMVDRPtr,
     SubbandMVDRGSCPtr, SubbandDS, SubbandGSC, SubbandGSCRLS, SubbandMVDR, SubbandMVDRGSC, calc_all_delays,
+    DOAEstimatorSRPBasePtr, DOAEstimatorSRPDSBLAPtr, DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA,
 )
 
-__all__ = ['SSPEED', 'SnapShotArrayPtr', 'SpectralMatrixArrayPtr', 'SubbandDSPtr', 'SubbandGSCPtr', 'SubbandGSCRLSPtr', 'SubbandMVDRPtr', 'SubbandMVDRGSCPtr', 'SubbandDS', 'SubbandGSC', 'SubbandGSCRLS', 'SubbandMVDR', 'SubbandMVDRGSC', 'calc_all_delays']
+__all__ = ['SSPEED', 'SnapShotArrayPtr', 'SpectralMatrixArrayPtr', 'SubbandDSPtr', 'SubbandGSCPtr', 'SubbandGSCRLSPtr', 'SubbandMVDRPtr', 'SubbandMVDRGSCPtr', 'SubbandDS', 'SubbandGSC', 'SubbandGSCRLS', 'SubbandMVDR', 'SubbandMVDRGSC', 'calc_all_delays',
+           'DOAEstimatorSRPBasePtr', 'DOAEstimatorSRPDSBLAPtr', 'DOAEstimatorSRPBase', 'DOAEstimatorSRPDSBLA']

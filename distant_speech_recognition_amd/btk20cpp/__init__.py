@@ -151,8 +151,10 @@ OverSampledDFTAnalysisBank, OverSampledDFTSynthesisBank = _mod.OverSampledDFTAna
 SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _mod.SubbandGSCRLSPtr
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
 ZelinskiPostFilter, McCowanPostFilter, LefkimmiatisPostFilter = _mod.ZelinskiPostFilterPtr, _mod.McCowanPostFilterPtr, _mod.LefkimmiatisPostFilterPtr
+DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA = _mod.DOAEstimatorSRPBasePtr, _mod.DOAEstimatorSRPDSBLAPtr
 
 __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TYPE_APAB", "TYPE_ZELINSKI2", "NO_USE_POST_FILTER",
             "jarithmetic_error", "jinitialization_error", "jkey_error", "jparse_error", "jtype_error", "jiterator_error", "calc_all_delays",
             "SampleFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SubbandDS", "SubbandGSC", "SubbandGSCRLS",
-            "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter"]
+            "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
+            "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA"]

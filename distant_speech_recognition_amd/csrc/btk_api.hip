@@ -183,6 +183,66 @@ int btk_weights_mainlobe_halfband(int M, int N, float samplerate, const double* 
   return BTK_OK;
 }
 
+// The search grid of DOAEstimatorSRPDSBLA::calc_steering_unit_table_ (beamformer.cc:3052, :3071) in the reference's own types:
+// set_search_param stores float parameters (:2999-3013), the count is (unsigned)((max - min) / width + 0.5) and the angle is
+// accumulated in double.  thetas_out may be null (count only).
+int btk_srp_grid(float min_theta, float max_theta, float width_theta, int* n_theta, double* thetas_out)
+{
+  if (!n_theta) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_grid: null argument");
+  if (min_theta > max_theta)
+    return btk_set_error(BTK_ERR_PARAMETER, "Invalid argument: minTheta %f > maxTheta %f\n", min_theta, max_theta);
+  if (!(width_theta > 0.f)) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_grid: widthTheta %f must be positive", width_theta);
+  const double cnt = (max_theta - min_theta) / width_theta + 0.5;
+  if (!(cnt < 1.0e6)) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_grid: %g grid points", cnt);
+  const unsigned n = (unsigned)cnt;
+  *n_theta = (int)n;
+  if (thetas_out) {
+    unsigned i = 0;
+    for (double theta = min_theta; i < n; theta += width_theta, i++) thetas_out[i] = theta;
+  }
+  return BTK_OK;
+}
+
+// DOAEstimatorSRPDSBLA::set_look_direction_ (beamformer.cc:3193-3207): channel n lags channel 0 by |p_n - p_0| cos(theta), with
+// theta passed as a float as the reference's signature has it.  positions are seconds (metres over the speed of sound).
+int btk_srp_delays(int N, const double* positions, double theta, double* delays_out)
+{
+  if (N < 1 || !positions || !delays_out) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_delays: bad argument");
+  const float th = (float)theta;
+  delays_out[0] = 0.0;
+  for (int c = 1; c < N; c++) delays_out[c] = std::fabs(positions[c] - positions[0]) * std::cos((double)th);
+  return BTK_OK;
+}
+
+// The steering table svTbl_ of calc_steering_unit_table_ (beamformer.cc:3046-3089): out complex128 [U][K][N], K = M/2 + 1; row
+// [u][k] = wq_k of calcMainlobe for the delays of theta_u on bins fbin_min .. fbin_max, ones in bin 0, zero elsewhere.
+int btk_srp_table(int M, int N, float samplerate, const double* positions, int n_theta, const double* thetas, int fbin_min,
+                  int fbin_max, double* out)
+{
+  if (!positions || !thetas || !out) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_table: null argument");
+  if (M < 2 || (M & (M - 1))) return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_table: M=%d must be a power of two", M);
+  if (N < 2) return btk_set_error(BTK_ERR_DIMENSION, "btk_srp_table: N=%d channels, need at least 2", N);
+  if (n_theta < 1) return btk_set_error(BTK_ERR_DIMENSION, "btk_srp_table: %d grid points", n_theta);
+  if (fbin_min < 1 || fbin_min > fbin_max || fbin_max > M / 2)
+    return btk_set_error(BTK_ERR_PARAMETER, "btk_srp_table: frequency range %d .. %d, need 1 <= fbinMin <= fbinMax <= %d", fbin_min,
+                         fbin_max, M / 2);
+  const int K = M / 2 + 1;
+  std::vector<double> delays(N);
+  std::vector<cd> wq((size_t)M * N);
+  cd* tbl = reinterpret_cast<cd*>(out);
+  for (int u = 0; u < n_theta; u++) {
+    int rc = btk_srp_delays(N, positions, thetas[u], delays.data());
+    if (!rc) rc = btk_weights_mainlobe(M, N, samplerate, delays.data(), reinterpret_cast<double*>(wq.data()));
+    if (rc) return rc;
+    cd* row = tbl + (size_t)u * K * N;
+    for (size_t i = 0; i < (size_t)K * N; i++) row[i] = cd(0.0, 0.0);
+    for (int c = 0; c < N; c++) row[c] = cd(1.0, 0.0);
+    for (int k = fbin_min; k <= fbin_max; k++)
+      for (int c = 0; c < N; c++) row[(size_t)k * N + c] = wq[(size_t)k * N + c];
+  }
+  return BTK_OK;
+}
+
 // calc_blocking_matrix_ (beamformer.cc:373-454): classical Gram-Schmidt over the first N-NC
 // columns of the projector I - conj(a) a^T / |a|^2.
 int btk_weights_blocking_matrix(const double* a_in, int N, int NC, double* B_out)

@@ -1209,3 +1209,157 @@ def wpe_apply(X, G, M, lower_num=0, upper_num=32, band_width=0.0, samplerate=160
     lo, up = wpe_band(M, band_width, samplerate)
     check(_lib.lib().btk_wpe_apply(_ptr(X), _ptr(G), _ptr(out), S, K, Cn, T, T, lower_num, upper_num, lo, up, _stream()))
     return out
+
+
+# ---------------------------------------------------------------------------- steered response power (DOA estimation)
+SRP_RESET_RP = -10e10                # the reset value of an N-best entry (beamformer.cc:3131-3135); its DOA is (-pi, -pi), index -1
+SRP_MAX_NBEST = 16
+
+
+def srp_grid(min_theta=-np.pi / 2, max_theta=np.pi / 2, width_theta=0.1):
+    """The search grid of DOAEstimatorSRPDSBLA (beamformer.cc:3052, :3071): float parameters, (unsigned)((max - min) / width
+    + 0.5) points, the angle accumulated in double -> thetas float64 [nTheta]."""
+    n = C.c_int(0)
+    L = _lib.lib()
+    check(L.btk_srp_grid(float(min_theta), float(max_theta), float(width_theta), C.byref(n), None))
+    thetas = np.zeros(n.value, np.float64)
+    check(L.btk_srp_grid(float(min_theta), float(max_theta), float(width_theta), C.byref(n), _np_ptr(thetas)))
+    return thetas
+
+
+def srp_delays(positions, theta):
+    """set_look_direction_ (beamformer.cc:3193-3207): |p_n - p_0| cos(theta) with theta rounded to float as the reference
+    passes it; positions in seconds (metres over the speed of sound)."""
+    pos = np.ascontiguousarray(positions, np.float64)
+    d = np.zeros(pos.shape[0], np.float64)
+    check(_lib.lib().btk_srp_delays(pos.shape[0], _np_ptr(pos), float(theta), _np_ptr(d)))
+    return d
+
+
+def srp_table(M, N, samplerate, positions, thetas, fbin_min=1, fbin_max=None):
+    """svTbl_ (beamformer.cc:3046-3089) -> complex128 [nTheta][M/2+1][N]: calcMainlobe rows on bins fbin_min .. fbin_max,
+    ones in bin 0, zero elsewhere."""
+    pos = np.ascontiguousarray(positions, np.float64)
+    th = np.ascontiguousarray(thetas, np.float64)
+    if pos.shape != (N,):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "Number of positions does not match number of channels (%d vs. %d)." % (pos.size, N))
+    fbin_max = M // 2 if fbin_max is None else int(fbin_max)
+    out = np.zeros((th.shape[0], M // 2 + 1, N), np.complex128)
+    check(_lib.lib().btk_srp_table(M, N, float(samplerate), _np_ptr(pos), th.shape[0], _np_ptr(th), int(fbin_min), fbin_max, _np_ptr(out)))
+    return out
+
+
+class SRPTable:
+    """A steering table on the device in the operand order of srp_power_kernel (btk_srp_pack_table)."""
+
+    def __init__(self, table, device):
+        table = np.ascontiguousarray(table, np.complex128)
+        if table.ndim != 3:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "steering table has shape %s, expected [U][K][N]" % (table.shape,))
+        self.U, self.K, self.N = (int(v) for v in table.shape)
+        L = _lib.lib()
+        packed = np.zeros(L.btk_srp_packed_elems(self.U, self.K, self.N), np.complex64)
+        check(L.btk_srp_pack_table(_np_ptr(table), self.U, self.K, self.N, _np_ptr(packed)))
+        self.packed = torch.from_numpy(packed).to(device)
+
+
+def srp_power(X, table, M, fbin_min=1, fbin_max=None):
+    """Response power of every grid direction and frame, and the frame energy, in one pass over X (calc_response_power_ /
+    calc_energy, beamformer.cc:3091-3122, 3221-3251).  X complex64 [S][K][N][T] (a row-padded view will do), table an SRPTable
+    or a complex128 [U][K][N] array -> (rp float32 [S][U][T], energy float32 [S][T])."""
+    ts = _check(X, "X", torch.complex64, 4, rows=True)
+    S, K, N, T = X.shape
+    if K != M // 2 + 1:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "X has %d bins, M = %d needs %d" % (K, M, M // 2 + 1))
+    if not isinstance(table, SRPTable):
+        table = SRPTable(table, X.device)
+    if (table.K, table.N) != (K, N) or table.packed.device != X.device:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "steering table [%d][%d][%d] does not match X %s" % (table.U, table.K, table.N, tuple(X.shape)))
+    fbin_max = M // 2 if fbin_max is None else int(fbin_max)
+    rp = torch.empty((S, table.U, T), dtype=torch.float32, device=X.device)
+    energy = torch.empty((S, T), dtype=torch.float32, device=X.device)
+    check(_lib.lib().btk_srp_power(_ptr(X), _ptr(table.packed), _ptr(rp), _ptr(energy), S, M, N, ts, T, table.U,
+                                   int(fbin_min), fbin_max, _stream()))
+    return rp, energy
+
+
+def srp_select(rp, energy, nbest, threshold=0.0, acc=None):
+    """Per-frame N-best list (strict >: of equal powers the earlier grid index ranks first), energy gate and accumulated powers
+    (beamformer.cc:3131-3187).  rp float32 [S][U][T], energy float32 [S][T] -> (nbest_rp float32 [S][T][nbest], nbest_idx int32
+    [S][T][nbest], gate int32 [S][T], acc float64 [S][U]); a gated frame keeps (SRP_RESET_RP, -1); acc is updated in place."""
+    _check(rp, "rp", torch.float32, 3)
+    S, U, T = rp.shape
+    _check(energy, "energy", torch.float32, (S, T))
+    if acc is None:
+        acc = torch.zeros((S, U), dtype=torch.float64, device=rp.device)
+    _check(acc, "acc", torch.float64, (S, U))
+    nbest = int(nbest)
+    nb_rp = torch.empty((S, T, max(nbest, 0)), dtype=torch.float32, device=rp.device)
+    nb_idx = torch.empty((S, T, max(nbest, 0)), dtype=torch.int32, device=rp.device)
+    gate = torch.empty((S, T), dtype=torch.int32, device=rp.device)
+    check(_lib.lib().btk_srp_select(_ptr(rp), _ptr(energy), float(threshold), nbest, _ptr(nb_rp), _ptr(nb_idx), _ptr(gate),
+                                    _ptr(acc), S, U, T, _stream()))
+    return nb_rp, nb_idx, gate, acc
+
+
+def srp_nbest_host(values, nbest):
+    """The insertion loop of get_nbest_hypotheses_from_accrp_ (beamformer.cc:2942-2981) over one row of powers: (values, indices),
+    (SRP_RESET_RP, -1) where nothing was inserted."""
+    best, idx = [SRP_RESET_RP] * nbest, [-1] * nbest
+    for u, rp in enumerate(np.asarray(values, np.float64)):
+        if rp > best[nbest - 1]:
+            for n1 in range(nbest):
+                if rp > best[n1]:
+                    best[n1 + 1:] = best[n1:nbest - 1]
+                    idx[n1 + 1:] = idx[n1:nbest - 1]
+                    best[n1], idx[n1] = float(rp), u
+                    break
+    return np.array(best, np.float64), np.array(idx, np.int64)
+
+
+class SRPState:
+    """What S estimators share and keep between blocks: the grid and the steering table (fixed at construction: another
+    geometry, search range or frequency range is another SRPState), the last grid direction's weights, and accRPs_ in float64
+    on the device."""
+
+    def __init__(self, S, M, samplerate, positions, device, nbest=1, min_theta=-np.pi / 2, max_theta=np.pi / 2, width_theta=0.1,
+                 min_phi=-np.pi / 2, fbin_min=1, fbin_max=None, energy_threshold=0.0):
+        self.S, self.M, self.samplerate, self.device, self.nbest = S, M, samplerate, device, int(nbest)
+        self.positions = np.ascontiguousarray(positions, np.float64)
+        self.N = self.positions.shape[0]
+        self.min_phi = float(np.float32(min_phi))
+        self.energy_threshold = float(energy_threshold)
+        self.fbin_min, self.fbin_max = int(fbin_min), M // 2 if fbin_max is None else int(fbin_max)
+        self.thetas = srp_grid(min_theta, max_theta, width_theta)
+        self.table_host = srp_table(M, self.N, samplerate, self.positions, self.thetas, self.fbin_min, self.fbin_max)
+        self.table = SRPTable(self.table_host, device)
+        w_last = self.table_host[-1].astype(np.complex64)         # what next() leaves in vector_: zero outside fbin_min .. fbin_max
+        w_last[: self.fbin_min] = 0
+        self.w_last = torch.from_numpy(w_last).to(device)
+        self.acc = torch.zeros((S, self.thetas.shape[0]), dtype=torch.float64, device=device)
+
+    def init_accs(self):
+        self.acc.zero_()
+
+    def process(self, X):
+        """One block: (rp, energy, nbest_rp, nbest_idx, gate); acc grows by the block's gated powers."""
+        rp, energy = srp_power(X, self.table, self.M, self.fbin_min, self.fbin_max)
+        nb_rp, nb_idx, gate, _ = srp_select(rp, energy, self.nbest, self.energy_threshold, self.acc)
+        return rp, energy, nb_rp, nb_idx, gate
+
+    def last_beam(self, X):
+        """The delay-and-sum output of the last grid direction (what next() leaves in vector_, beamformer.cc:3101-3115):
+        complex64 [S][K][T], zero outside fbin_min .. fbin_max."""
+        return bf_apply(self.w_last, X)
+
+    def final_nbest_hypotheses(self):
+        """final_nbest_hypotheses (beamformer.cc:2942-2981) per stream: (rps float64 [S][nbest], doas float64 [S][nbest][2]) with
+        DOA (theta_u, minPhi), (-pi, -pi) where nothing was inserted."""
+        acc = self.acc.cpu().numpy()
+        rps = np.zeros((self.S, self.nbest)); doas = np.full((self.S, self.nbest, 2), -np.pi)
+        for s in range(self.S):
+            rps[s], idx = srp_nbest_host(acc[s], self.nbest)
+            for j, u in enumerate(idx):
+                if u >= 0:
+                    doas[s, j] = (self.thetas[u], self.min_phi)
+        return rps, doas

@@ -5,6 +5,7 @@
 #include <complex>
 #include <functional>
 #include <list>
+#include <memory>
 #include <vector>
 #include "stream/stream.h"
 #include "modulated/modulated.h"
@@ -405,6 +406,91 @@ class SubbandMVDRGSC : public SubbandMVDR {
   bool normalize_weight_;
 };
 typedef Inherit<SubbandMVDRGSC, SubbandMVDRPtr> SubbandMVDRGSCPtr;
+
+// Direction-of-arrival estimation by the steered response power of a delay-and-sum beam over a grid of directions (reference
+// beamformer.h:466-569, beamformer.cc:2876-3251).  The base keeps the search grid, the frequency range, the per-frame N-best list
+// and the powers accumulated over the utterance; DOAEstimatorSRPDSBLA is the linear-array estimator.
+class DOAEstimatorSRPBase {
+ public:
+  DOAEstimatorSRPBase(unsigned nBest, unsigned fbinMax);
+  virtual ~DOAEstimatorSRPBase();
+  const gsl_vector* nbest_rps() const { return nBestRPs_; }
+  const gsl_matrix* nbest_doas() const { return argMaxDOAs_; }
+  // [nTheta][1], the powers of the last frame that passed the energy gate.  (The reference allocates it only under a debug macro
+  // that is defined after the allocation site, so as compiled it writes through a null pointer; here it always exists.)
+  const gsl_matrix* response_power_matrix() const { return rpMat_; }
+  float energy() const { return energy_; }
+  void final_nbest_hypotheses() { get_nbest_hypotheses_from_accrp_(); }
+  void set_energy_threshold(float engeryThreshold) { engery_threshold_ = engeryThreshold; }
+  // (a new range rebuilds the steering table and keeps the accumulated powers; the reference keeps a table with zeros outside
+  //  the old range)
+  void set_frequency_range(unsigned fbinMin, unsigned fbinMax);
+  void init_accs() { init_accs_(); }
+  void set_search_param(float minTheta = -M_PI / 2, float maxTheta = M_PI / 2, float minPhi = -M_PI / 2, float maxPhi = M_PI / 2,
+                        float widthTheta = 0.1, float widthPhi = 0.1);
+  const gsl_vector* getNBestRPs() { return nbest_rps(); }                                       // ENABLE_LEGACY_BTK_API aliases
+  const gsl_matrix* getNBestDOAs() { return nbest_doas(); }
+  const gsl_matrix* getResponsePowerMatrix() { return response_power_matrix(); }
+  float getEnergy() { return energy(); }
+  void getFinalNBestHypotheses() { final_nbest_hypotheses(); }
+  void setEnergyThreshold(float engeryThreshold) { set_energy_threshold(engeryThreshold); }
+  void setFrequencyRange(unsigned fbinMin, unsigned fbinMax) { set_frequency_range(fbinMin, fbinMax); }
+  void initAccs() { init_accs(); }
+  void setSearchParam(float minTheta = -M_PI / 2, float maxTheta = M_PI / 2, float minPhi = -M_PI / 2, float maxPhi = M_PI / 2,
+                      float widthTheta = 0.1, float widthPhi = 0.1)
+  { set_search_param(minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi); }
+  // the grid and the accumulated powers (accRPs_) as they stand after the frame next() served last
+  const std::vector<double>& search_thetas() const { return thetas_; }
+  const std::vector<double>& accumulated_rps() const { return accRPs_; }
+  unsigned nbest() const { return nBest_; }
+ protected:
+  void clear_table_();
+  void reset_nbest_();
+  void alloc_grid_();             // nTheta_ / thetas_ by the grid rule, rpMat_ sized; accRPs_ zeroed unless the grid is the one it was accumulated on
+  virtual void get_nbest_hypotheses_from_accrp_();
+  virtual void init_accs_();
+  float widthTheta_, widthPhi_, minTheta_, maxTheta_, minPhi_, maxPhi_;
+  unsigned nTheta_, nPhi_, fbinMin_, fbinMax_, nBest_;
+  bool table_initialized_;
+  std::vector<double> thetas_, accRPs_;
+  gsl_vector* nBestRPs_;
+  gsl_matrix* argMaxDOAs_;
+  gsl_matrix* rpMat_;
+  std::vector<gsl_matrix*> rpMat_retired_;   // earlier sizes of rpMat_: a caller may still hold a view of one
+  float engery_threshold_, energy_;
+};
+
+// The linear-array estimator (reference beamformer.h:542-566).  Usage as there: construct, set_array_geometry(positions over the
+// speed of sound), set the channels, call next().  It works on blocks like every node here: the block's snapshots go through
+// btk_srp_power / btk_srp_select once, the block's N-best lists, energies, powers and the last grid direction's beam come down once,
+// and next() serves them frame by frame -- after next() returned frame t, nbest_rps(), nbest_doas(), energy(),
+// response_power_matrix() and the accumulated powers describe frame t: the powers are accumulated on the host as the frames are
+// served (final_nbest_hypotheses() / init_accs() may come between any two frames), in float64 and in frame order like the
+// reference.  There is no recursion over frames, so the result does not depend on the block size.
+class DOAEstimatorSRPDSBLA : public DOAEstimatorSRPBase, public SubbandDS {
+ public:
+  DOAEstimatorSRPDSBLA(unsigned nBest, unsigned samplerate, unsigned fftLen, const String& nm = "DOAEstimatorSRPDSBLA");
+  ~DOAEstimatorSRPDSBLA();
+  virtual const gsl_vector_complex* next(int frame_no = -5);
+  virtual void reset();           // the channels and the frame counter start over; the accumulated powers stay (beamformer.cc:3209-3219)
+  void set_array_geometry(gsl_vector* positions);
+  void setArrayGeometry(gsl_vector* positions) { set_array_geometry(positions); }
+ protected:
+  virtual void calc_steering_unit_table_();
+  virtual bool advance_chunk_();
+ private:
+  void run_block_();
+  unsigned samplerate_;
+  std::vector<double> positions_;
+  unsigned table_chanN_, table_fbinMin_, table_fbinMax_;
+  std::vector<float> last_row_;   // the last grid direction's weights, complex64 [K][N], zero outside the frequency range
+  DeviceBuffer dTable_, dRp_, dEnergy_, dNbRp_, dNbIdx_, dGate_;
+  std::vector<float> rp_h_, energy_h_, nbrp_h_;
+  std::vector<int> nbidx_h_, gate_h_;
+  bool block_ran_;
+};
+typedef std::shared_ptr<DOAEstimatorSRPBase> DOAEstimatorSRPBasePtr;   // the reference's refcount_ptr: the class is not Countable
+typedef Inherit<DOAEstimatorSRPDSBLA, SubbandDSPtr> DOAEstimatorSRPDSBLAPtr;
 
 // Many utterance graphs advanced as ONE launch (not part of the reference's interface).  The reference's unit of work is one
 // graph per utterance (unit_test/test_online_beamforming.py:80-88 builds SampleFeature x N -> OverSampledDFTAnalysisBank x N ->

@@ -3160,6 +3160,225 @@ const gsl_vector_complex* SubbandGSCRLS::next(int frame_no)
 }
 
 
+// ================================================================================ DOAEstimatorSRPBase / DOAEstimatorSRPDSBLA
+// (reference beamformer/beamformer.cc:2876-3251)
+DOAEstimatorSRPBase::DOAEstimatorSRPBase(unsigned nBest, unsigned fbinMax)
+    : widthTheta_(0.25), widthPhi_(0.25), minTheta_(-M_PI), maxTheta_(M_PI), minPhi_(-M_PI), maxPhi_(M_PI), nTheta_(0), nPhi_(1),
+      fbinMin_(1), fbinMax_(fbinMax), nBest_(nBest), table_initialized_(false), rpMat_(gsl_matrix_alloc(0, 1)),
+      engery_threshold_(0.0), energy_(0.0)
+{
+  if (nBest < 1 || nBest > 16) throw jparameter_error("DOAEstimatorSRPBase: nBest %d, need 1 .. 16\n", (int)nBest);
+  nBestRPs_ = gsl_vector_calloc(nBest_);
+  argMaxDOAs_ = gsl_matrix_alloc(nBest_, 2);
+}
+
+DOAEstimatorSRPBase::~DOAEstimatorSRPBase()
+{
+  gsl_vector_free(nBestRPs_);
+  gsl_matrix_free(argMaxDOAs_);
+  gsl_matrix_free(rpMat_);
+  for (size_t i = 0; i < rpMat_retired_.size(); i++) gsl_matrix_free(rpMat_retired_[i]);
+}
+
+// (:2916-2939: the table and the accumulated powers go together)
+void DOAEstimatorSRPBase::clear_table_()
+{
+  if (table_initialized_) accRPs_.clear();
+  table_initialized_ = false;
+}
+
+void DOAEstimatorSRPBase::reset_nbest_()
+{
+  for (unsigned n = 0; n < nBest_; n++) {
+    gsl_vector_set(nBestRPs_, n, -10e10);
+    gsl_matrix_set(argMaxDOAs_, n, 0, -M_PI);
+    gsl_matrix_set(argMaxDOAs_, n, 1, -M_PI);
+  }
+}
+
+void DOAEstimatorSRPBase::alloc_grid_()
+{
+  int n = 0;
+  check_abi(btk_srp_grid(minTheta_, maxTheta_, widthTheta_, &n, NULL));
+  nTheta_ = (unsigned)n; nPhi_ = 1;
+  std::vector<double> th(nTheta_, 0.0);
+  check_abi(btk_srp_grid(minTheta_, maxTheta_, widthTheta_, &n, th.data()));
+  // the reference zeroes the accumulated powers with every table build (:3065-3067); here they survive a rebuild that leaves the
+  // grid as it was (a new frequency range, another channel count) -- set_search_param / set_array_geometry have cleared them
+  if (th != thetas_ || accRPs_.size() != nTheta_) accRPs_.assign(nTheta_, 0.0);
+  thetas_.swap(th);
+  if (rpMat_->size1 != nTheta_) { rpMat_retired_.push_back(rpMat_); rpMat_ = gsl_matrix_alloc(nTheta_, 1); }
+  for (size_t i = 0; i < rpMat_->size1; i++) gsl_matrix_set(rpMat_, i, 0, 0.0);
+}
+
+// (:2942-2981) the insertion loop over the accumulated powers; the second coordinate is minPhi, as there
+void DOAEstimatorSRPBase::get_nbest_hypotheses_from_accrp_()
+{
+  reset_nbest_();
+  for (unsigned u = 0; u < accRPs_.size(); u++) {
+    const double rp = accRPs_[u];
+    if (!(rp > gsl_vector_get(nBestRPs_, nBest_ - 1))) continue;
+    for (unsigned n1 = 0; n1 < nBest_; n1++)
+      if (rp > gsl_vector_get(nBestRPs_, n1)) {
+        for (unsigned n2 = nBest_ - 1; n2 > n1; n2--) {
+          gsl_vector_set(nBestRPs_, n2, gsl_vector_get(nBestRPs_, n2 - 1));
+          gsl_matrix_set(argMaxDOAs_, n2, 0, gsl_matrix_get(argMaxDOAs_, n2 - 1, 0));
+          gsl_matrix_set(argMaxDOAs_, n2, 1, gsl_matrix_get(argMaxDOAs_, n2 - 1, 1));
+        }
+        gsl_vector_set(nBestRPs_, n1, rp);
+        gsl_matrix_set(argMaxDOAs_, n1, 0, thetas_[u]);
+        gsl_matrix_set(argMaxDOAs_, n1, 1, (double)minPhi_);
+        break;
+      }
+  }
+}
+
+void DOAEstimatorSRPBase::init_accs_()
+{
+  std::fill(accRPs_.begin(), accRPs_.end(), 0.0);
+  for (size_t i = 0; i < rpMat_->size1; i++) gsl_matrix_set(rpMat_, i, 0, 0.0);
+  reset_nbest_();
+}
+
+void DOAEstimatorSRPBase::set_search_param(float minTheta, float maxTheta, float minPhi, float maxPhi, float widthTheta, float widthPhi)
+{
+  if (minTheta > maxTheta) throw jparameter_error("Invalid argument: minTheta %f > maxTheta %f\n", minTheta, maxTheta);
+  if (minPhi > maxPhi) throw jparameter_error("Invalid argument: minPhi %f > maxPhi %f\n", minPhi, maxPhi);
+  minTheta_ = minTheta; maxTheta_ = maxTheta; minPhi_ = minPhi; maxPhi_ = maxPhi; widthTheta_ = widthTheta; widthPhi_ = widthPhi;
+  clear_table_();
+}
+
+void DOAEstimatorSRPBase::set_frequency_range(unsigned fbinMin, unsigned fbinMax) { fbinMin_ = fbinMin; fbinMax_ = fbinMax; }
+
+DOAEstimatorSRPDSBLA::DOAEstimatorSRPDSBLA(unsigned nBest, unsigned samplerate, unsigned fftLen, const String& nm)
+    : DOAEstimatorSRPBase(nBest, fftLen / 2), SubbandDS(fftLen, false, nm), samplerate_(samplerate), table_chanN_(0),
+      table_fbinMin_(0), table_fbinMax_(0), block_ran_(false)
+{
+  set_search_param();                                            // the derived defaults replace the base's (:3026)
+  reset_nbest_();
+  want_snapshots();
+}
+
+DOAEstimatorSRPDSBLA::~DOAEstimatorSRPDSBLA() {}
+
+void DOAEstimatorSRPDSBLA::set_array_geometry(gsl_vector* positions)
+{
+  positions_.resize(positions->size);
+  for (size_t i = 0; i < positions->size; i++) positions_[i] = gsl_vector_get(positions, i);
+  clear_table_();
+}
+
+// svTbl_ (:3046-3089) on the device in the kernel's operand order.  Built on the first frame and again whenever the geometry, the
+// search range, the frequency range or the number of channels has changed since.
+void DOAEstimatorSRPDSBLA::calc_steering_unit_table_()
+{
+  const unsigned N = chanN(), K = fftLen2_ + 1;
+  if (N == 0) throw jparameter_error("DOAEstimatorSRPDSBLA:calc_steering_unit_table_():: Set the channel\n");
+  if (positions_.empty()) throw jparameter_error("DOAEstimatorSRPDSBLA: call set_array_geometry() once\n");
+  if (positions_.size() != N)
+    throw jdimension_error("DOAEstimatorSRPDSBLA: %d microphone positions for %d channels\n", (int)positions_.size(), (int)N);
+  alloc_grid_();
+  if (nTheta_ == 0) throw jparameter_error("DOAEstimatorSRPDSBLA: the search range holds no grid point\n");
+  std::vector<cd> tbl((size_t)nTheta_ * K * N);
+  check_abi(btk_srp_table((int)fftLen_, (int)N, (float)samplerate_, positions_.data(), (int)nTheta_, thetas_.data(), (int)fbinMin_,
+                          (int)fbinMax_, reinterpret_cast<double*>(tbl.data())));
+  std::vector<float> packed((size_t)2 * btk_srp_packed_elems((int)nTheta_, (int)K, (int)N));
+  check_abi(btk_srp_pack_table(reinterpret_cast<const double*>(tbl.data()), (int)nTheta_, (int)K, (int)N, packed.data()));
+  h2d(dTable_.ensure(sizeof(float) * packed.size()), packed.data(), sizeof(float) * packed.size());
+  last_row_.assign((size_t)2 * K * N, 0.f);
+  const cd* last = &tbl[(size_t)(nTheta_ - 1) * K * N];
+  for (size_t i = (size_t)fbinMin_ * N; i < (size_t)(fbinMax_ + 1) * N; i++) { last_row_[2 * i] = (float)last[i].real(); last_row_[2 * i + 1] = (float)last[i].imag(); }
+  table_chanN_ = N; table_fbinMin_ = fbinMin_; table_fbinMax_ = fbinMax_;
+  table_initialized_ = true;
+  block_ran_ = false;
+}
+
+// The current block through the two launches and the last direction's apply; everything next() serves comes down once.
+void DOAEstimatorSRPDSBLA::run_block_()
+{
+  ScopedNs timer(g_device_ns);
+  const unsigned N = chanN(), K = fftLen2_ + 1, U = nTheta_;
+  const long T = T_;
+  const size_t Tn = (size_t)(T ? T : 1);
+  rp_h_.assign((size_t)U * T, 0.f); energy_h_.assign((size_t)T, 0.f); nbrp_h_.assign((size_t)T * nBest_, 0.f);
+  nbidx_h_.assign((size_t)T * nBest_, -1); gate_h_.assign((size_t)T, 0); Yhost_.assign((size_t)2 * K * T, 0.f);
+  if (T > 0) {
+    void* dX = snapshots_();
+    void* dRp = dRp_.ensure(sizeof(float) * U * Tn);
+    void* dEn = dEnergy_.ensure(sizeof(float) * Tn);
+    void* dNr = dNbRp_.ensure(sizeof(float) * nBest_ * Tn);
+    void* dNi = dNbIdx_.ensure(sizeof(int) * nBest_ * Tn);
+    void* dG = dGate_.ensure(sizeof(int) * Tn);
+    check_abi(btk_srp_power(dX, dTable_.get(), dRp, dEn, 1, (int)fftLen_, (int)N, T, T, (int)U, (int)fbinMin_, (int)fbinMax_, nstream()));
+    // (no device accumulator: the node serves per-frame state, so accRPs_ grows on the host as the frames are served)
+    check_abi(btk_srp_select(dRp, dEn, engery_threshold_, (int)nBest_, dNr, dNi, dG, NULL, 1, (int)U, T, nstream()));
+    void* dW = dWBuf_.ensure(sizeof(float) * last_row_.size());
+    h2d(dW, last_row_.data(), sizeof(float) * last_row_.size());
+    void* dY = dYBuf_.ensure(sizeof(float) * 2 * K * Tn);
+    check_abi(btk_bf_apply(dW, 0, dX, dY, 1, (int)K, (int)N, T, T, nstream()));
+    d2h_async(rp_h_.data(), dRp, sizeof(float) * rp_h_.size());
+    d2h_async(energy_h_.data(), dEn, sizeof(float) * energy_h_.size());
+    d2h_async(nbrp_h_.data(), dNr, sizeof(float) * nbrp_h_.size());
+    d2h_async(nbidx_h_.data(), dNi, sizeof(int) * nbidx_h_.size());
+    d2h_async(gate_h_.data(), dG, sizeof(int) * gate_h_.size());
+    d2h(Yhost_.data(), dY, sizeof(float) * Yhost_.size());
+  }
+  block_ran_ = true;
+}
+
+bool DOAEstimatorSRPDSBLA::advance_chunk_()
+{
+  block_ran_ = false;
+  return SubbandDS::advance_chunk_();
+}
+
+// (:3124-3191)
+const gsl_vector_complex* DOAEstimatorSRPDSBLA::next(int frame_no)
+{
+  if (frame_no == frame_no_) return vector_;
+  if (halfBandShift_) throw j_error("halfBandShift_ == true is not implemented yet\n");
+  reset_nbest_();
+  if (!table_initialized_ || table_chanN_ != chanN() || table_fbinMin_ != fbinMin_ || table_fbinMax_ != fbinMax_) calc_steering_unit_table_();
+  ensure_chunk_();
+  const long idx = frame_no_ + 1;
+  while (idx >= chunk_base_ + T_)
+    if (!advance_chunk_()) { is_end_ = true; throw jiterator_error("end of samples!"); }
+  if (!block_ran_) run_block_();
+  const long t = idx - chunk_base_, T = T_;
+  const unsigned U = nTheta_;
+  energy_ = energy_h_[t];
+  if (gate_h_[t]) {
+    for (unsigned u = 0; u < U; u++) {
+      const double rp = (double)rp_h_[(size_t)u * T + t];
+      accRPs_[u] += rp;                                          // (:3162; srp_acc_kernel adds the same numbers in the same order)
+      gsl_matrix_set(rpMat_, u, 0, rp);
+    }
+    for (unsigned n = 0; n < nBest_; n++) {
+      const int u = nbidx_h_[(size_t)t * nBest_ + n];
+      if (u < 0) continue;
+      gsl_vector_set(nBestRPs_, n, (double)nbrp_h_[(size_t)t * nBest_ + n]);
+      gsl_matrix_set(argMaxDOAs_, n, 0, thetas_[u]);
+      gsl_matrix_set(argMaxDOAs_, n, 1, 0.0);
+    }
+    // vector_: the delay-and-sum output of the last grid direction on the bins of the range and their mirrors (:3101-3115)
+    const float* Y = Yhost_.data();
+    for (unsigned k = fbinMin_; k <= fbinMax_; k++) {
+      const double re = Y[2 * ((size_t)k * T + t)], im = Y[2 * ((size_t)k * T + t) + 1];
+      vector_->data[2 * k] = re; vector_->data[2 * k + 1] = im;
+      if (k < fftLen2_) { vector_->data[2 * (fftLen_ - k)] = re; vector_->data[2 * (fftLen_ - k) + 1] = -im; }
+    }
+  }
+  increment_();
+  return vector_;
+}
+
+// (:3209-3219) the accumulated powers survive
+void DOAEstimatorSRPDSBLA::reset()
+{
+  SubbandDS::reset();
+  block_ran_ = false;
+}
+
 // ================================================================================ WPE dereverberation
 // (reference dereverberation/dereverberation.cc:40-307, 312-760)
 namespace {

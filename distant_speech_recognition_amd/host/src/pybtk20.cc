@@ -164,6 +164,39 @@ class PyStream : public Base, public BlockSource {
 typedef PyStream<VectorFloatFeatureStream, gsl_vector_float, float> PyVectorFloatFeatureStream;
 typedef PyStream<VectorComplexFeatureStream, gsl_vector_complex, cd> PyVectorComplexFeatureStream;
 
+// the methods of DOAEstimatorSRPBase (beamformer.i:677-708) on a bound class T that derives from it.  nbest_rps / nbest_doas /
+// response_power_matrix are numpy VIEWS of the estimator's own storage (kept alive by the array), like next()'s vector.
+template <class T, class Cls>
+void def_srp_base(Cls& cls)
+{
+  auto vec = [](py::object self) { const gsl_vector* v = self.cast<T&>().nbest_rps();
+    return py::array(py::array_t<double>({(py::ssize_t)v->size}, {(py::ssize_t)sizeof(double)}, v->data, self)); };
+  auto doa = [](py::object self) { const gsl_matrix* a = self.cast<T&>().nbest_doas();
+    return py::array(py::array_t<double>({(py::ssize_t)a->size1, (py::ssize_t)a->size2}, {(py::ssize_t)(sizeof(double) * a->tda), (py::ssize_t)sizeof(double)}, a->data, self)); };
+  auto mat = [](py::object self) { const gsl_matrix* a = self.cast<T&>().response_power_matrix();
+    return py::array(py::array_t<double>({(py::ssize_t)a->size1, (py::ssize_t)a->size2}, {(py::ssize_t)(sizeof(double) * a->tda), (py::ssize_t)sizeof(double)}, a->data, self)); };
+  auto search = [](T& e, float minTheta, float maxTheta, float minPhi, float maxPhi, float widthTheta, float widthPhi) {
+    e.set_search_param(minTheta, maxTheta, minPhi, maxPhi, widthTheta, widthPhi); };
+  cls.def("nbest_rps", vec).def("getNBestRPs", vec)
+      .def("nbest_doas", doa).def("getNBestDOAs", doa)
+      .def("response_power_matrix", mat).def("getResponsePowerMatrix", mat)
+      .def("energy", [](T& e) { return e.energy(); }).def("getEnergy", [](T& e) { return e.energy(); })
+      .def("final_nbest_hypotheses", [](T& e) { e.final_nbest_hypotheses(); })
+      .def("getFinalNBestHypotheses", [](T& e) { e.final_nbest_hypotheses(); })
+      .def("set_energy_threshold", [](T& e, float th) { e.set_energy_threshold(th); }, py::arg("engeryThreshold"))
+      .def("setEnergyThreshold", [](T& e, float th) { e.set_energy_threshold(th); }, py::arg("engeryThreshold"))
+      .def("set_frequency_range", [](T& e, unsigned lo, unsigned hi) { e.set_frequency_range(lo, hi); }, py::arg("fbinMin"), py::arg("fbinMax"))
+      .def("setFrequencyRange", [](T& e, unsigned lo, unsigned hi) { e.set_frequency_range(lo, hi); }, py::arg("fbinMin"), py::arg("fbinMax"))
+      .def("init_accs", [](T& e) { e.init_accs(); }).def("initAccs", [](T& e) { e.init_accs(); })
+      .def("set_search_param", search, py::arg("minTheta") = (float)(-M_PI / 2), py::arg("maxTheta") = (float)(M_PI / 2),
+           py::arg("minPhi") = (float)(-M_PI / 2), py::arg("maxPhi") = (float)(M_PI / 2), py::arg("widthTheta") = 0.1f, py::arg("widthPhi") = 0.1f)
+      .def("setSearchParam", search, py::arg("minTheta") = (float)(-M_PI / 2), py::arg("maxTheta") = (float)(M_PI / 2),
+           py::arg("minPhi") = (float)(-M_PI / 2), py::arg("maxPhi") = (float)(M_PI / 2), py::arg("widthTheta") = 0.1f, py::arg("widthPhi") = 0.1f)
+      // the grid and the accumulated powers as they stand after the frame served last (copies)
+      .def("search_thetas", [](T& e) { const std::vector<double>& v = e.search_thetas(); return py::array_t<double>((py::ssize_t)v.size(), v.data()); })
+      .def("accumulated_rps", [](T& e) { const std::vector<double>& v = e.accumulated_rps(); return py::array_t<double>((py::ssize_t)v.size(), v.data()); });
+}
+
 // a bound node is used as it is; any other Python object with size() / __iter__ / next() / reset() becomes a source node (the
 // reference wants the explicit PyVector*FeatureStreamPtr(obj) wrapper, stream/pyStream.h:25-168; both spellings work here)
 VectorComplexFeatureStreamPtr as_cstream(const py::object& o)
@@ -497,6 +530,23 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("calc_blocking_matrix2", &SubbandMVDRGSC::calc_blocking_matrix2)
       .def("upgrade_blocking_matrix", &SubbandMVDRGSC::upgrade_blocking_matrix)
       .def("blocking_matrix_output", [](SubbandMVDRGSC& b, int outChanX) { return copy_of(b.blocking_matrix_output(outChanX)); }, py::arg("outChanX") = 0);
+
+  // ---- DOA estimation (beamformer.i:674-757)
+  {
+    py::class_<DOAEstimatorSRPBase, std::shared_ptr<DOAEstimatorSRPBase>> base(m, "DOAEstimatorSRPBasePtr");
+    base.def(py::init([](unsigned nBest, unsigned fbinMax) { return std::make_shared<DOAEstimatorSRPBase>(nBest, fbinMax); }),
+             py::arg("nBest"), py::arg("fbinMax"));
+    def_srp_base<DOAEstimatorSRPBase>(base);
+    // (the node base is the class's SECOND base, as in the reference: its subobject does not start where the object does)
+    py::class_<DOAEstimatorSRPDSBLA, SubbandDS, cref<DOAEstimatorSRPDSBLA>> dsb(m, "DOAEstimatorSRPDSBLAPtr", py::multiple_inheritance());
+    dsb.def(py::init([](unsigned nBest, unsigned samplerate, unsigned fftlen, const std::string& nm) {
+              return new DOAEstimatorSRPDSBLA(nBest, samplerate, fftlen, nm); }),
+            py::arg("nBest"), py::arg("samplerate"), py::arg("fftlen"), py::arg("nm") = "DOAEstimatorSRPDSBLAPtr");
+    def_srp_base<DOAEstimatorSRPDSBLA>(dsb);
+    auto geom = [](DOAEstimatorSRPDSBLA& e, py::array_t<double, py::array::c_style | py::array::forcecast> positions) {
+      GslVec v(positions); e.set_array_geometry(v.v); };
+    dsb.def("set_array_geometry", geom, py::arg("positions")).def("setArrayGeometry", geom, py::arg("positions"));
+  }
 
   // ---- postfilter/postfilter.h
   py::class_<ZelinskiPostFilter, VectorComplexFeatureStream, cref<ZelinskiPostFilter>>(m, "ZelinskiPostFilterPtr")

@@ -469,6 +469,38 @@ int  btk_weights_sidelobe(const double* B, const double* wa, int N, int NC, doub
 int  btk_weights_gsc_effective(const double* wq, const double* wl, int M, int N,
                                int normalize, float* w_out);
 
+/* ---- Steered response power: DOAEstimatorSRPBase / DOAEstimatorSRPDSBLA (beamformer.h:466-569) ----------------------
+ * The search grid of calc_steering_unit_table_ (beamformer.cc:3052, :3071) in the reference's types: float parameters,
+ * n = (unsigned)((max - min) / width + 0.5), theta accumulated in double.  thetas_out [host] float64 [n] or null (count
+ * only).  min > max is the parameter error of set_search_param (:2999-3006).                                             */
+int  btk_srp_grid(float min_theta, float max_theta, float width_theta, int* n_theta, double* thetas_out);
+/* set_look_direction_ (:3193-3207): delays [host] float64 [N], |p_n - p_0| cos(theta), theta rounded to float as there;
+ * positions [host] float64 [N] in seconds (positions over the speed of sound).                                           */
+int  btk_srp_delays(int N, const double* positions, double theta, double* delays_out);
+/* svTbl_ (:3046-3089): out [host] complex128 [n_theta][M/2+1][N]; row [u][k] is wq_k of btk_weights_mainlobe for the
+ * delays of theta_u on bins fbin_min .. fbin_max, ones in bin 0, zero elsewhere.                                         */
+int  btk_srp_table(int M, int N, float samplerate, const double* positions, int n_theta, const double* thetas,
+                   int fbin_min, int fbin_max, double* out);
+/* The table in the operand order of the kernel: packed [host] complex64, btk_srp_packed_elems(U, K, N) elements
+ * ([K][PP][UP][2], element [k][p][u][h] = sv[u][k][2p+h], zero beyond N and U; PP, UP: pairs / directions rounded up to
+ * the register chunk and to 32).  Copy it to the device once per table.                                                  */
+long btk_srp_packed_elems(int U, int K, int N);
+int  btk_srp_pack_table(const double* table, int U, int K, int N, float* packed);
+/* calc_response_power_ for every grid direction and frame of a block, and calc_energy (:3091-3122, :3221-3251), one pass
+ * over X [dev] complex64 [S][M/2+1][N][T_stride] on the fp32 matrix cores; the beams are never written.
+ *   rp [dev] float32 [S][U][T] = sum_{k=fmin}^{fmax} c_k |sv[u][k]^H x_k[t]|^2 / (fmax - fmin + 1), c_k = 2 (k < M/2), 1
+ *   energy [dev] float32 [S][T] = sum_k c_k (sum_n |x_k[n][t]|^2)^2 / (M N)
+ * N = 2 .. 256, 1 <= fbin_min <= fbin_max <= M/2.  Directions run in passes of up to 128; for N <= 64 a pass reads X once,
+ * for N > 64 the 32-frame strip is fetched again for each of its up to four 32-direction tiles (from cache at best).     */
+int  btk_srp_power(const void* X, const void* table_packed, void* rp, void* energy, int S, int M, int N, long T_stride,
+                   long T, int U, int fbin_min, int fbin_max, void* stream);
+/* The per-frame N-best insertion (strict >, :3157-3187), the energy gate (:3148-3155) and accRPs_ (:3162):
+ *   nbest_rp [dev] float32 [S][T][nbest], nbest_idx [dev] int32 [S][T][nbest] (-10e10 / -1 where nothing was inserted),
+ *   gate [dev] int32 [S][T] = !(energy < threshold), acc [dev] float64 [S][U] += gate rp, frame by frame in index order
+ *   (NULL: no accumulation, for a caller that accumulates frame by frame itself).  nbest <= 16.                          */
+int  btk_srp_select(const void* rp, const void* energy, float threshold, int nbest, void* nbest_rp, void* nbest_idx,
+                    void* gate, void* acc, int S, int U, long T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
