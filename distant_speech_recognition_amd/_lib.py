@@ -134,6 +134,11 @@ SIGNATURES = {
     "btk_srp_pack_table": (_i, [_vp, _i, _i, _i, _vp]),
     "btk_srp_power": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _i, _i, _i, _vp]),
     "btk_srp_select": (_i, [_vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _l, _vp]),
+    "btk_hos_max_channels": (_i, []),
+    "btk_hos_workspace_bytes": (_l, [_i, _i, _i, _i, _l]),
+    "btk_hos_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp, _vp, _vp, _vp]),
+    "btk_hos_minimize": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _i, _d, _d, _i, _d,
+                              _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -1363,3 +1363,99 @@ class SRPState:
                 if u >= 0:
                     doas[s, j] = (self.thetas[u], self.min_phi)
         return rps, doas
+
+
+# ------------------------------------------------------------------ maximum-empirical-kurtosis beamformers (csrc/hos_kernels.hip)
+HOS_DEFAULTS = dict(maxiter=40, gtol=1.0e-2, mindelta=1.0e-5, max_halvings=30, armijo_c1=1.0e-4)
+
+
+class HOSState:
+    """Previous statistics of SubbandMEKBeamformer (reset_stats / store_stats, lib/pybeamformer.py:1613-1627) on the device:
+    prevAvgY2, prevAvgY4 float64 [K][NS] and prevFrameN int64 [K][NS]."""
+
+    def __init__(self, K, NS, device):
+        self.K, self.NS, self.device = int(K), int(NS), device
+        self.reset()
+
+    def reset(self):
+        self.prevAvgY2 = torch.zeros((self.K, self.NS), dtype=torch.float64, device=self.device)
+        self.prevAvgY4 = torch.zeros((self.K, self.NS), dtype=torch.float64, device=self.device)
+        self.prevFrameN = torch.zeros((self.K, self.NS), dtype=torch.int64, device=self.device)
+
+    def store(self, stats, frames):
+        """store_stats for every bin and source, as written there: prevFrameN grows FIRST, then every frame adds
+        Y2 / prevFrameN and Y4 / prevFrameN with Y2 = sum_s |Y_s|^2 / NS and Y4 = Y2^2 -- not a running mean.  stats: what
+        hos_eval returned for the final weights, frames: the number of frames it saw."""
+        self.prevFrameN += int(frames)
+        n = self.prevFrameN.to(torch.float64)
+        NS = self.NS
+        self.prevAvgY2 += stats[:, 2 * NS:2 * NS + 1] / n
+        self.prevAvgY4 += stats[:, 2 * NS + 1:2 * NS + 2] / n
+
+
+def _hos_inputs(X, wuH, BmH, Nc, mask, state):
+    ts = _check(X, "X", torch.complex64, 3, rows=True)
+    K, N, T = X.shape
+    _check(wuH, "wuH", torch.complex128, (None, K, N))
+    NS = wuH.shape[0]
+    _check(BmH, "BmH", torch.complex128, (NS, K, None, N))
+    Nc = int(Nc)
+    if BmH.shape[2] != N - Nc:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "BmH has %d rows, N - Nc = %d" % (BmH.shape[2], N - Nc))
+    if mask is not None:
+        _check(mask, "mask", torch.float32, (T,))
+    if state is not None:
+        _check(state.prevAvgY2, "prevAvgY2", torch.float64, (K, NS))
+        _check(state.prevAvgY4, "prevAvgY4", torch.float64, (K, NS))
+        _check(state.prevFrameN, "prevFrameN", torch.int64, (K, NS))
+    null = C.c_void_p(0)
+    prev = (null, null, null) if state is None else (_ptr(state.prevAvgY2), _ptr(state.prevAvgY4), _ptr(state.prevFrameN))
+    return ts, K, N, T, NS, Nc, (null if mask is None else _ptr(mask)), prev
+
+
+def hos_eval(X, wuH, BmH, x=None, Nc=1, alpha=0.01, beta=3.0, gamma=-1.0, normalize=False, mask=None, state=None, grad=True):
+    """fun_hos_bf and dfun_hos_bf (lib/pybeamformer.py:1548-1593) of the MEK (normalize=False) or NMEK beamformer for every bin
+    in one launch.  X complex64 [K][N][T] (a row-padded view will do), wuH complex128 [NS][K][N], BmH complex128
+    [NS][K][N-Nc][N], x float64 [K][2 NS (N-Nc)] packed active weights (None: zero), mask float32 [T] of 0/1 or None, state an
+    HOSState or None -> (fun float64 [K], grad float64 [K][D] or None, stats float64 [K][2 NS + 2]).  A mask that selects no
+    frame, with zero previous statistics, divides by zero as the reference's empty list of observations does: fun and grad are NaN."""
+    ts, K, N, T, NS, Nc, pmask, prev = _hos_inputs(X, wuH, BmH, Nc, mask, state)
+    D = 2 * NS * (N - Nc)
+    if x is not None:
+        _check(x, "x", torch.float64, (K, D))
+    fun = torch.empty((K,), dtype=torch.float64, device=X.device)
+    g = torch.empty((K, D), dtype=torch.float64, device=X.device) if grad else None
+    stats = torch.empty((K, 2 * NS + 2), dtype=torch.float64, device=X.device)
+    check(_lib.lib().btk_hos_eval(_ptr(X), pmask, _ptr(wuH), _ptr(BmH), C.c_void_p(0) if x is None else _ptr(x), float(alpha),
+                                  float(beta), float(gamma), int(bool(normalize)), prev[0], prev[1], prev[2], K, N, Nc, NS, ts, T,
+                                  _ptr(fun), C.c_void_p(0) if g is None else _ptr(g), _ptr(stats), _stream()))
+    return fun, g, stats
+
+
+HOSResult = collections.namedtuple("HOSResult", "x f iters trace_f trace_halvings")
+
+
+def hos_minimize(X, wuH, BmH, x0=None, Nc=1, alpha=0.01, beta=3.0, gamma=-1.0, normalize=True, mask=None, state=None, **options):
+    """The optimisation of every bin in one launch (estimate_active_weights, lib/pybeamformer.py:1802-1827, with the
+    Polak-Ribiere+ / Armijo iteration of DESIGN.md 3.15): inputs as hos_eval, options as HOS_DEFAULTS -> HOSResult(x float64
+    [K][D], f float64 [K], iters int32 [K], trace_f float64 [K][maxiter], trace_halvings int32 [K][maxiter])."""
+    unknown = set(options) - set(HOS_DEFAULTS)
+    if unknown:
+        raise TypeError("hos_minimize: unknown options %s" % sorted(unknown))
+    o = dict(HOS_DEFAULTS, **options)
+    ts, K, N, T, NS, Nc, pmask, prev = _hos_inputs(X, wuH, BmH, Nc, mask, state)
+    D = 2 * NS * (N - Nc)
+    if x0 is not None:
+        _check(x0, "x0", torch.float64, (K, D))
+    maxiter = int(o["maxiter"])
+    dev = X.device
+    xo = torch.empty((K, D), dtype=torch.float64, device=dev)
+    fo = torch.empty((K,), dtype=torch.float64, device=dev)
+    it = torch.empty((K,), dtype=torch.int32, device=dev)
+    tf = torch.empty((K, max(maxiter, 0)), dtype=torch.float64, device=dev)
+    th = torch.empty((K, max(maxiter, 0)), dtype=torch.int32, device=dev)
+    check(_lib.lib().btk_hos_minimize(_ptr(X), pmask, _ptr(wuH), _ptr(BmH), C.c_void_p(0) if x0 is None else _ptr(x0), float(alpha),
+                                      float(beta), float(gamma), int(bool(normalize)), prev[0], prev[1], prev[2], K, N, Nc, NS, ts,
+                                      T, maxiter, float(o["gtol"]), float(o["mindelta"]), int(o["max_halvings"]),
+                                      float(o["armijo_c1"]), _ptr(xo), _ptr(fo), _ptr(it), _ptr(tf), _ptr(th), _stream()))
+    return HOSResult(xo, fo, it, tf, th)

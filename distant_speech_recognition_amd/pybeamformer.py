@@ -9,6 +9,8 @@ iterator behaviour; the per-frame / per-bin numpy loops are replaced by HIP kern
     SubbandMVDRBeamformer         :540-585   super-directive (diffuse-noise MVDR)
     SubbandGSCLMSBeamformer       :588-762   adaptive NLMS canceller   -> btk_nlms_process
     SubbandSMIMVDRBeamformer      :930-1019  sample-matrix-inversion MVDR -> btk_cov_* + btk_mvdr_weights
+    SubbandHOSBatchBeamformer, SubbandMEKBeamformer, SubbandNMEKBeamformer, fun_hos_bf, dfun_hos_bf, pack_weights,
+    unpack_weights                :1331-1860 maximum-empirical-kurtosis GSC -> btk_hos_eval / btk_hos_minimize
 """
 import numpy as np
 
@@ -153,6 +155,16 @@ class SubbandBeamformer(object):
 
     def shiftlen(self):
         return self._shiftlen
+
+    def calc_entire_weights(self):
+        """pybeamformer.py:440-450: wqH alone, or wqH - waH BmH for the bins 0 .. fftlen / 2 of an [fftlen][N] array"""
+        assert self._wqH is not None, "The quiescent beamformer weights have to be computed"
+        if self._BmH is None or self._waH is None:
+            return self._wqH
+        woH = np.zeros((self._fftlen, self._chan_num), complex)
+        for m in range(self._fftlen2 + 1):
+            woH[m][:] = self._wqH[m] - np.dot(self._waH[m], self._BmH[m])
+        return woH
 
     def set_active_weights(self):
         if self._beamformer is None:
@@ -609,3 +621,317 @@ class SubbandGEVBeamformer(SubbandBlindMVDRBeamformer):
         # the target covariance stays un-normalised: no impact on the GEV solution (:1317-1318)
         engine.cov_finalize(self._noise_covariance_matrices, self._noise_frame_counts, gamma=max(gamma, 0.0))
         engine.cov_trace_normalize(self._noise_covariance_matrices)
+
+
+# ------------------------------------------------------------------ higher-order-statistics batch beamformers
+def _hos_select_frames(energies, time_delta, target_labs, energy_threshold, R):
+    """Stream indices of the frames accum_observations keeps (pybeamformer.py:1406-1424), walking the VAD segments exactly as
+    that loop does: a frame past the end of the current segment only moves on to the next segment (the `elif`), it is not
+    looked at again; within a segment a frame is kept if its energy exceeds the threshold and frx % R == 0."""
+    selected, labx = [], 0
+    for frx, energy in enumerate(energies):
+        elapsed_time = frx * time_delta
+        if labx < len(target_labs):
+            if elapsed_time >= target_labs[labx][0] and (elapsed_time <= target_labs[labx][1] or target_labs[labx][1] < 0):
+                if energy > energy_threshold and (frx % R) == 0:
+                    selected.append(frx)
+            elif elapsed_time > target_labs[labx][1]:
+                labx += 1
+    return np.array(selected, np.int64)
+
+
+def unpack_weights(packed_weights, num_vecotrs, dim):
+    """pybeamformer.py:1508-1521: float vector (re, im, re, im, ...) -> complex [num_vectors][dim]"""
+    p = np.asarray(packed_weights, float)[: 2 * num_vecotrs * dim]
+    return (p[0::2] + 1j * p[1::2]).reshape(num_vecotrs, dim)
+
+
+def pack_weights(weights, num_vecotrs, dim):
+    """pybeamformer.py:1524-1539: complex [num_vectors][dim] -> float vector (re, im, re, im, ...)"""
+    w = np.array([np.asarray(weights[m], complex)[:dim] for m in range(num_vecotrs)]).reshape(-1)
+    packed_weights = np.zeros(2 * num_vecotrs * dim, float)
+    packed_weights[0::2], packed_weights[1::2] = w.real, w.imag
+    return packed_weights
+
+
+def fun_hos_bf(x, fbinX, hos_beamformer):
+    """pybeamformer.py:1548-1569: the objective the optimiser minimises, at one bin (evaluated on the GPU)"""
+    return hos_beamformer._eval_f(fbinX, x, grad=False)[0]
+
+
+def dfun_hos_bf(x, fbinX, hos_beamformer):
+    """pybeamformer.py:1572-1593: its gradient in the reference's convention (half the derivative, no Jacobian of the clamp)"""
+    return hos_beamformer._eval_f(fbinX, x, grad=True)[1]
+
+
+class SubbandHOSBatchBeamformer(_OwnBlocks, SubbandBeamformer):
+    """pybeamformer.py:1331-1505: GSC whose active weights maximise a higher-order statistic of the output over the
+    accumulated observations.  The observations stay on the device as complex64 [K][N][Tobs]; objective, gradient and the
+    optimisation of all bins run there (btk_hos_eval / btk_hos_minimize)."""
+
+    _normalize = False
+
+    def __init__(self, upper_beamformers, src_index=0, Nc=1, alpha=0.01):
+        if Nc > 2:
+            raise NotImplementedError('N implemented in the case of NC > 2')
+        SubbandBeamformer.__init__(self, upper_beamformers[src_index].spec_sources())
+        self._upper_beamformers = upper_beamformers
+        self._num_sources = len(upper_beamformers)
+        self._Nc = Nc
+        self._half_band_shift = False
+        self._srcX = src_index
+        self._isamp = 0
+        self._alpha = alpha
+        self._front = SubbandDSPtr(fftlen=self._fftlen, half_band_shift=False)    # owns channels + device snapshots
+        for source in self._spec_sources:
+            self._front.set_channel(source)
+        self._beamformer = self._front
+        self._observations = None          # numpy [Tobs][K][N], the reference's list of snapshots
+        self._observations_dev = None      # device complex64 [K][N][Tobs]
+        self._selected_frames = None
+        self._wuH = None
+        self._BmH = None
+        self._wuH_dev = self._BmH_dev = None
+        self._woH = np.zeros((self._num_sources, self._fftlen2 + 1, self._chan_num), complex)
+        self._Y = None
+        self._frames = None
+
+    def reset(self):
+        self._front.reset()
+        self._isamp = 0
+        self._Y = None
+        self._frames = None
+
+    def accum_observations(self, samplerate, target_labs=[(0.0, -1)], energy_threshold=10, R=1):
+        """pybeamformer.py:1385-1426.  Returns a numpy copy [Tobs][K][N] of the selected snapshots."""
+        import torch
+        blocks, energies = [], []
+        for base, X in self._snapshot_blocks():
+            blocks.append(X[0].clone())            # the front may reuse its block buffer
+            energies.append(engine.frame_energy(X, self._fftlen)[0].cpu().numpy())
+        energies = np.concatenate(energies)
+        sel = _hos_select_frames(energies, self.shiftlen() / float(samplerate), target_labs, energy_threshold, R)
+        self._selected_frames = sel
+        K = self._fftlen2 + 1
+        obs = torch.empty((K, self._chan_num, len(sel)), dtype=torch.complex64, device=device())
+        pos, base = 0, 0
+        for Xb in blocks:                                  # compaction of the selected frames of every block: plumbing
+            T = Xb.shape[-1]
+            idx = sel[(sel >= base) & (sel < base + T)] - base
+            if len(idx):
+                obs[:, :, pos:pos + len(idx)] = Xb[:, :, torch.from_numpy(idx).to(Xb.device)]
+                pos += len(idx)
+            base += T
+        self._observations_dev = obs
+        self._observations = np.ascontiguousarray(obs.permute(2, 0, 1).cpu().numpy())
+        self._front.reset()          # the reference drained its sources here; they are re-read afterwards
+        return self._observations
+
+    def set_observations(self, X):
+        """observations from anywhere else: complex [Tobs][K][N] (numpy, rounded to complex64)"""
+        import torch
+        self._observations = np.ascontiguousarray(np.asarray(X).astype(np.complex64))
+        self._observations_dev = torch.from_numpy(np.ascontiguousarray(self._observations.transpose(1, 2, 0))).to(device())
+
+    def alpha(self):
+        return self._alpha
+
+    def num_sources(self):
+        return self._num_sources
+
+    def Nc(self):
+        return self._Nc
+
+    def reset_stats(self):
+        pass
+
+    def store_stats(self):
+        pass
+
+    def norm_active_weight_vectors(self, fbinX, wa_f):
+        return wa_f
+
+    def set_upper_beamformer_weights(self, wuH):
+        """wuH complex [num_sources][>= K][N]: the blocking matrices of calc_upper_beamformer_weights (:1456-1466) for them"""
+        import torch
+        K = self._fftlen2 + 1
+        self._wuH = np.array([np.asarray(w, complex) for w in wuH])
+        self._BmH = np.zeros((self._num_sources, K, self._chan_num - self._Nc, self._chan_num), complex)
+        for srcX in range(self._num_sources):
+            for m in range(K):
+                self._BmH[srcX][m] = np.transpose(calc_blocking_matrix(np.conjugate(self._wuH[srcX][m]), self._Nc))
+        self._wuH_dev = torch.from_numpy(np.ascontiguousarray(self._wuH[:, :K])).to(device())
+        self._BmH_dev = torch.from_numpy(self._BmH).to(device())
+
+    def calc_upper_beamformer_weights(self):
+        """pybeamformer.py:1452-1466"""
+        self.set_upper_beamformer_weights([bf.calc_entire_weights() for bf in self._upper_beamformers])
+
+    def device_block(self):
+        import torch
+        if self._Y is None:
+            assert self._wuH is not None, "calculate upper beamformers' weights"
+            X = self._front.device_snapshots()
+            W = torch.from_numpy(np.conjugate(self._woH[self._srcX]).astype(np.complex64)).to(device())
+            self._Y = engine.bf_apply(W, X)
+        return self._Y
+
+    def __iter__(self):
+        assert self._wuH is not None, "calculate upper beamformers' weights"
+        for frame in self._iter_blocks():
+            self._isamp += 1
+            yield frame
+
+
+class SubbandMEKBeamformer(SubbandHOSBatchBeamformer):
+    """pybeamformer.py:1596-1827: maximum empirical kurtosis beamformer.
+
+    usage: construct with the upper beamformers, accum_observations(), estimate_active_weights(), iterate."""
+    _OFFSET = -1E+6
+
+    def __init__(self, upper_beamformers, src_index=0, Nc=1, alpha=0.01, beta=3.0):
+        SubbandHOSBatchBeamformer.__init__(self, upper_beamformers, src_index=src_index, Nc=Nc, alpha=alpha)
+        self._beta = beta
+        self._gamma = -1.0
+        self.reset_stats()
+
+    def reset_stats(self):
+        self._state = engine.HOSState(self._fftlen2 + 1, self._num_sources, device())
+
+    _prevAvgY2 = property(lambda self: self._state.prevAvgY2.cpu().numpy())
+    _prevAvgY4 = property(lambda self: self._state.prevAvgY4.cpu().numpy())
+    _prevFrameN = property(lambda self: self._state.prevFrameN.cpu().numpy())
+
+    def _eval(self, x, grad=True):
+        """all bins at the packed weights x float64 [K][D] (None: zero): (fun [K], grad [K][D] or None, stats) on the device"""
+        assert self._wuH is not None, "calculate upper beamformer weights"
+        assert self._observations_dev is not None, "accumulate observations"
+        return engine.hos_eval(self._observations_dev, self._wuH_dev, self._BmH_dev, x, Nc=self._Nc, alpha=self._alpha,
+                               beta=self._beta, gamma=self._gamma, normalize=self._normalize, state=self._state, grad=grad)
+
+    def _eval_f(self, fbinX, x, grad=True, normalize=None, alpha=None):
+        """one bin at the packed weights x: (fun float, grad float64 [D] or None).  The launch is given that bin's rows only
+        (the kernel runs one workgroup per bin it is given); normalize / alpha default to the beamformer's own."""
+        import torch
+        k = slice(fbinX, fbinX + 1)
+        st = engine.HOSState(1, self._num_sources, device())
+        st.prevAvgY2, st.prevAvgY4, st.prevFrameN = (self._state.prevAvgY2[k].contiguous(), self._state.prevAvgY4[k].contiguous(),
+                                                     self._state.prevFrameN[k].contiguous())
+        xs = torch.from_numpy(np.ascontiguousarray(x, np.float64)[None]).to(device())
+        f, g, _ = engine.hos_eval(self._observations_dev[k], self._wuH_dev[:, k].contiguous(), self._BmH_dev[:, k].contiguous(),
+                                  xs, Nc=self._Nc, alpha=self._alpha if alpha is None else alpha, beta=self._beta,
+                                  gamma=self._gamma, normalize=self._normalize if normalize is None else normalize, state=st,
+                                  grad=grad)
+        return float(f[0].item()), (None if g is None else g[0].cpu().numpy())
+
+    def norm_active_weight_vectors(self, fbinX, wa):
+        return wa
+
+    def calc_obj_func(self, fbinX, wa_f):
+        """pybeamformer.py:1632-1656: kurtosis of the outputs (+ _OFFSET) for the active weights wa_f [num_sources][N - Nc],
+        taken as they are (the callers normalise first): fun_hos_bf without its sign and regulariser"""
+        dim = self._chan_num - self._Nc
+        x = pack_weights(np.asarray(wa_f, complex), self._num_sources, dim)
+        return -self._eval_f(fbinX, x, grad=False, normalize=False, alpha=0.0)[0]
+
+    def gradient(self, fbinX, wa_f):
+        """pybeamformer.py:1658-1683 for weights taken as they are: complex [num_sources][N - Nc]"""
+        dim = self._chan_num - self._Nc
+        x = pack_weights(np.asarray(wa_f, complex), self._num_sources, dim)
+        g = self._eval_f(fbinX, x, grad=True, normalize=False, alpha=0.0)[1]
+        return -unpack_weights(g, self._num_sources, dim)
+
+    def _normalized(self, packed):
+        """norm_active_weight_vectors for every bin: packed float64 [K][D] -> complex [K][num_sources][N - Nc]"""
+        K, dim = self._fftlen2 + 1, self._chan_num - self._Nc
+        wa = np.stack([unpack_weights(packed[m], self._num_sources, dim) for m in range(K)])
+        return np.stack([np.array(self.norm_active_weight_vectors(m, wa[m])) for m in range(K)])
+
+    def _finalize(self, packed, bins=None):
+        """finalize_wa_f (:1789-1800) for the given bins (default: all): store_stats and _woH.  Unlike the reference, whose
+        loop over m overwrites _woH of EVERY bin with the current bin's active weights, bin m keeps its own."""
+        import torch
+        K = self._fftlen2 + 1
+        packed = np.ascontiguousarray(packed, np.float64)
+        wa = self._normalized(packed)
+        _, _, stats = self._eval(torch.from_numpy(packed).to(device()), grad=False)
+        if bins is None:
+            self._state.store(stats, self._observations_dev.shape[-1])
+        else:
+            keep = torch.zeros((K, 1), dtype=torch.bool, device=device())
+            keep[list(bins)] = True
+            old = self._state.prevAvgY2.clone(), self._state.prevAvgY4.clone(), self._state.prevFrameN.clone()
+            self._state.store(stats, self._observations_dev.shape[-1])
+            self._state.prevAvgY2 = torch.where(keep, self._state.prevAvgY2, old[0])
+            self._state.prevAvgY4 = torch.where(keep, self._state.prevAvgY4, old[1])
+            self._state.prevFrameN = torch.where(keep, self._state.prevFrameN, old[2])
+        for m in (range(K) if bins is None else bins):
+            for srcX in range(self._num_sources):
+                self._woH[srcX][m] = self._wuH[srcX][m] - np.dot(np.conjugate(wa[m][srcX]), self._BmH[srcX][m])
+        self._Y = None
+        self._frames = None
+        return wa
+
+    def finalize_wa_f(self, fbinX, packed_wa):
+        """pybeamformer.py:1789-1800 for one bin"""
+        K = self._fftlen2 + 1
+        packed = np.zeros((K, 2 * self._num_sources * (self._chan_num - self._Nc)))
+        packed[fbinX] = packed_wa
+        wa = self._finalize(packed, bins=[fbinX])
+        return pack_weights(wa[fbinX], self._num_sources, self._chan_num - self._Nc)
+
+    def estimate_wa_f_scipy(self, fbinX, startpoint, tolerance, solver='Nelder-Mead', options={'maxiter': 300}):
+        """pybeamformer.py:1767-1787: scipy.optimize.minimize with fun / dfun served by the GPU"""
+        import scipy.optimize
+        opt_result = scipy.optimize.minimize(fun_hos_bf, startpoint, args=(fbinX, self), method=solver, jac=dfun_hos_bf,
+                                             options=options)
+        return opt_result.x
+
+    def estimate_active_weights(self, module='device', solver='CG',
+                                options={'maxiter': 40, 'tolerance': 1.0E-03, 'gtol': 1.0E-02, 'mindelta': 1.0E-05, 'eps': 0.01}):
+        """pybeamformer.py:1802-1827.  module='device' (default) optimises every bin in one launch (engine.hos_minimize; solver is
+        ignored, options maxiter / gtol / mindelta / max_halvings / armijo_c1 are read); module='scipy' is the reference's bin by
+        bin flow; the pygsl solvers are not restated.  Returns the list of packed active weights per bin."""
+        K, dim = self._fftlen2 + 1, self._chan_num - self._Nc
+        self.calc_upper_beamformer_weights()
+        if module == 'device':
+            opts = {key: options[key] for key in engine.HOS_DEFAULTS if options.get(key) is not None}
+            res = engine.hos_minimize(self._observations_dev, self._wuH_dev, self._BmH_dev, None, Nc=self._Nc, alpha=self._alpha,
+                                      beta=self._beta, gamma=self._gamma, normalize=self._normalize, state=self._state, **opts)
+            self._last_result = res
+            packed = res.x.cpu().numpy()
+        elif module == 'scipy':
+            tolerance = options.get('tolerance')
+            sopts = {key: v for key, v in options.items() if key in ('maxiter', 'gtol', 'eps', 'disp')}
+            packed = np.zeros((K, 2 * self._num_sources * dim))
+            for m in range(K):
+                packed[m] = self.estimate_wa_f_scipy(m, np.zeros(2 * self._num_sources * dim, float), tolerance, solver, options=sopts)
+        elif module == 'pygsl':
+            raise ImportError('pygsl is not available; use module = "device" or "scipy"')
+        else:
+            raise ImportError('Install scipy or pygsl')
+        self._finalize(packed)
+        return [packed[m] for m in range(K)]
+
+
+class SubbandNMEKBeamformer(SubbandMEKBeamformer):
+    """pybeamformer.py:1830-1860: normalised maximum empirical kurtosis beamformer: the norm of every active weight vector
+    is clamped to |gamma| (gamma < 0: the norm of the upper-branch weights of the bin)."""
+    _normalize = True
+
+    def __init__(self, upper_beamformers, src_index=0, Nc=1, alpha=0.01, beta=3.0, gamma=-1.0):
+        SubbandMEKBeamformer.__init__(self, upper_beamformers, src_index, Nc, alpha, beta)
+        self._gamma = gamma
+
+    def normalize_weight(self, srcX, fbinX, wa):
+        nrm_wa = np.sqrt(np.inner(wa, np.conjugate(wa)).real)
+        if self._gamma < 0:
+            gamma = np.sqrt(np.inner(self._wuH[srcX][fbinX], np.conjugate(self._wuH[srcX][fbinX])))
+        else:
+            gamma = self._gamma
+        if nrm_wa > abs(gamma):
+            wa = abs(gamma) * wa / nrm_wa
+        return wa
+
+    def norm_active_weight_vectors(self, fbinX, wa_f):
+        return [self.normalize_weight(srcX, fbinX, wa_f[srcX]) for srcX in range(self._num_sources)]

@@ -501,6 +501,44 @@ int  btk_srp_power(const void* X, const void* table_packed, void* rp, void* ener
 int  btk_srp_select(const void* rp, const void* energy, float threshold, int nbest, void* nbest_rp, void* nbest_idx,
                     void* gate, void* acc, int S, int U, long T, void* stream);
 
+/* ---- Maximum-empirical-kurtosis GSC beamformers: SubbandMEKBeamformer / SubbandNMEKBeamformer (lib/pybeamformer.py:1596-1860)
+ * Shared inputs, for the bins k < K and the sources s < NS:
+ *   X [dev] complex64 [K][N][T_stride]      observation snapshots, frames contiguous
+ *   mask [dev] float32 [T] or NULL           only frames with mask != 0 count (the reference's list of observations)
+ *   wuH [dev] complex128 [NS][K][N]          upper-branch weights;  BmH [dev] complex128 [NS][K][N-Nc][N]
+ *   alpha, beta, gamma                       regulariser, kurtosis constant, norm bound (gamma < 0: ||wuH[s][k]||)
+ *   normalize                                0 = MEK, 1 = NMEK (the clamp of normalize_weight, :1845-1855)
+ *   prevAvgY2, prevAvgY4 [dev] float64 [K][NS], prevFrameN [dev] int64 [K][NS], or NULL for zero statistics
+ * N = 2 .. btk_hos_max_channels() (64), Nc = 1 or 2, NS = 1 or 2, T >= 1; BTK_ERR_DIMENSION otherwise.  All sums are
+ * float64 in a fixed order (no atomics): two calls give the same bits.                                                     */
+int  btk_hos_max_channels(void);
+/* Bytes of device workspace btk_hos_eval / btk_hos_minimize need for these sizes: 0 -- everything the kernels keep between
+ * their phases lives in LDS, neither entry takes a workspace argument.  Kept so that callers can size buffers uniformly.
+ * A mask that selects no frame, with zero previous statistics, divides by zero exactly as the reference's empty list of
+ * observations does: fun, grad and the optimiser's outputs of such a call are NaN, the statistics sums are 0.             */
+long btk_hos_workspace_bytes(int K, int N, int Nc, int NS, long T);
+/* fun_hos_bf and dfun_hos_bf (:1548-1593) over calc_obj_func and gradient (:1632-1683) at the packed weights
+ * x [dev] float64 [K][2 NS (N-Nc)] (NULL: zero), every bin in one launch:
+ *   fun [dev] float64 [K];  grad [dev] float64 [K][2 NS (N-Nc)] or NULL (objective only: the snapshots are read once)
+ *   stats [dev] float64 [K][2 NS + 2] or NULL: (sum_t |Y_s|^2, sum_t |Y_s|^4) per source, then sum_t m_t and sum_t m_t^2
+ *   with m_t = sum_s |Y_s[t]|^2 / NS, the frame terms of store_stats (:1618-1627).                                       */
+int  btk_hos_eval(const void* X, const void* mask, const void* wuH, const void* BmH, const void* x, double alpha, double beta,
+                  double gamma, int normalize, const void* prevAvgY2, const void* prevAvgY4, const void* prevFrameN, int K,
+                  int N, int Nc, int NS, long T_stride, long T, void* fun, void* grad, void* stats, void* stream);
+/* The per-bin optimisation of estimate_active_weights (:1802-1827) for every bin in one launch, one workgroup per bin, no host
+ * round trip: Polak-Ribiere+ conjugate gradients with Armijo backtracking from x0 [dev] float64 [K][D] (NULL: zero).  Per
+ * iteration: stop if ||g|| < gtol; d = -g if g.d >= 0; first trial step 2 / ||g|| in the first iteration, else twice the last
+ * accepted one; up to max_halvings halvings until fun(x + a d) <= f + armijo_c1 a g.d, stop if none; then
+ * d = -g' + max(0, g'.(g' - g) / g.g) d; stop if |f - f'| < mindelta.
+ *   x_out [dev] float64 [K][D], f_out [dev] float64 [K], iters_out [dev] int32 [K]
+ *   trace_f [dev] float64 [K][maxiter] accepted objective values (NaN where none)
+ *   trace_halvings [dev] int32 [K][maxiter] halvings of each iteration (-1: no step accepted, -2: iteration not reached)  */
+int  btk_hos_minimize(const void* X, const void* mask, const void* wuH, const void* BmH, const void* x0, double alpha,
+                      double beta, double gamma, int normalize, const void* prevAvgY2, const void* prevAvgY4,
+                      const void* prevFrameN, int K, int N, int Nc, int NS, long T_stride, long T, int maxiter, double gtol,
+                      double mindelta, int max_halvings, double armijo_c1, void* x_out, void* f_out, void* iters_out,
+                      void* trace_f, void* trace_halvings, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
