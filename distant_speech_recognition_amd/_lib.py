@@ -29,6 +29,7 @@ BTK_ERR_ALLOCATION = -3
 BTK_ERR_PARAMETER = -4
 BTK_ERR_HIP = -5
 BTK_ERR_NUMERIC = -6
+BTK_PF_MCCOWAN_RULES = 0x10      # type bit of btk_zelinski_process (include/btkhip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 

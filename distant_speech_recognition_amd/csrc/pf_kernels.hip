@@ -116,6 +116,9 @@ void zelinski_iir_kernel(float2* __restrict__ Y, const float2* __restrict__ Cc, 
   // the statistics (and the beamformer output the gain scales) of chunk i + 1 are requested before chunk i is scanned: the
   // 24 dependent cross-lane steps of a scan and the latency of a chunk's loads no longer add up
   const bool scales = type != 0;
+  // McCowan (BTK_PF_MCCOWAN_RULES): Re or |.| by type & 1 in EVERY frame (estimate_average_clean_PSD_ always reads type_,
+  // postfilter.cc:827-832) and the gain on every frame >= min_frames whatever the type (:889-894); `type` is never 0 then
+  const bool every_frame = (type & BTK_PF_MCCOWAN_RULES) != 0;
   // the 64-frame scan chunks sit on multiples of 64 of the STREAM's frame counter, not of this launch: a launch that starts
   // inside a chunk (history restarted mid-stream by a weight change) scans the same chunks whether the stream is processed in
   // one launch or block by block (the blocks of the node layer end on multiples of 64), hence the same roundings
@@ -145,12 +148,12 @@ void zelinski_iir_kernel(float2* __restrict__ Y, const float2* __restrict__ Cc, 
     const float phr = fmaf(a, phi_c.x, bb[0]), phim = fmaf(a, phi_c.y, bb[1]), ps = fmaf(a, psi_c, bb[2]);
     if (ok) {
       const bool apply = (g - 1) >= (long)min_frames;           // frame_no_ (= g-1, pre-increment) < min_frames -> NO_USE_POST_FILTER
-      const int pft = apply ? type : 0;
+      const int pft = (apply || every_frame) ? type : 0;
       float num = (pft & 1) ? fmaxf(phr, 0.f) : sqrtf(phr * phr + phim * phim);
       float Wf = (num / ps) * scale;
       if (Wf >= 1.0f) Wf = 1.0f;
       if (Wf < 1.0e-4f) Wf = 1.0e-4f;
-      if (apply && type != 0)                                   // NO_USE_POST_FILTER: the CSDs are just updated (postfilter.cc:197-199)
+      if (apply && scales)                                      // NO_USE_POST_FILTER: the CSDs are just updated (postfilter.cc:197-199)
         Y[row * T_stride + t] = make_float2(Wf * y.x, Wf * y.y);
       wlast = Wf;
     }
@@ -174,7 +177,7 @@ void zelinski_iir_kernel(float2* __restrict__ Y, const float2* __restrict__ Cc, 
 //     V_t = a_t V_{t-1} + b_t v_t,   v_t = sum_{i<=j} Cv[j][i] x'_i conj(x'_j)
 // with per-bin coefficient matrices built once from R (pf_coherence_coeff_kernel): off-diagonal 1/(1-R_ij) resp.
 // -1/(1-R_ij), diagonal = the collected (phi_ii + phi_jj)/2 terms.  McCowan: W = g(U) / Psi * 2/(N-1) -- the
-// Zelinski formula with Phi replaced by U, so btk_zelinski_process is reused.  Lefkimmiatis: W = g(U)/(g(U) + g(V)/L).
+// Zelinski formula with Phi replaced by U, so btk_zelinski_process is reused (type | BTK_PF_MCCOWAN_RULES).  Lefkimmiatis: W = g(U)/(g(U) + g(V)/L).
 //
 //   3. pf_coherence_coeff_kernel : R [K][N][N] -> Cs, Cv [K][N][N] (row j holds i <= j), float64 arithmetic
 //   4. bf_apply_stats2_kernel    : y_t, e_t and the quadratic forms u_t (v_t); lanes own frames, 16 rows of C at a

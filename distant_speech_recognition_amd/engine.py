@@ -801,6 +801,13 @@ class CoherencePostFilterState:
         self.Cs = self.Cv = self.lam = None
         self.frames_done = 0
 
+    def reset_csd(self):
+        """As ZelinskiState.reset_csd(): the CSD history restarts, the frame counter keeps counting (beamformer.cc:1082-1092)."""
+        self.u.zero_()
+        self.v.zero_()
+        self.psi.zero_()
+        self.w_last.zero_()
+
     def set_coherence(self, R, threshold=0.99):
         """R complex64 [K][N][N] (cuda): R_ after set_diffuse_noise_model / set_noise_spatial_spectral_matrix /
         diagonal loading (postfilter.cc:536-660); threshold = threshold_of_Rij_."""
@@ -865,8 +872,8 @@ def bf_apply_mccowan(W, D, X, state, alpha=0.6, type_=2, min_frames=0, out=None)
     L = _lib.lib()
     check(L.btk_bf_apply_stats2(_ptr(W), _ptr(D), int(W.shape[0] == S and S > 1), _ptr(X), _ptr(out), _ptr(state.Cs), None,
                                 _ptr(U), None, _ptr(Ee), S, K, N, ts, T, _stream()))
-    check(L.btk_zelinski_process(_ptr(out), _ptr(U), _ptr(Ee), S, K, N, ts, T, float(alpha), int(type_) & 3, int(min_frames),
-                                 state.frames_done, _ptr(state.u), _ptr(state.psi), _ptr(state.w_last), _stream()))
+    check(L.btk_zelinski_process(_ptr(out), _ptr(U), _ptr(Ee), S, K, N, ts, T, float(alpha), (int(type_) & 15) | _lib.BTK_PF_MCCOWAN_RULES,
+                                 int(min_frames), state.frames_done, _ptr(state.u), _ptr(state.psi), _ptr(state.w_last), _stream()))
     state.frames_done += T
     return out
 

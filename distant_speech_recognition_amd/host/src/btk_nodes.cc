@@ -2879,8 +2879,8 @@ void McCowanPostFilter::compute_(long from_frame)
       check_abi(btk_lefkimmiatis_process(Yo, Uo, Vo, dLamb_.get(), (int)fbinX1_, 1, (int)K, (int)N, T_, Tn, alpha_, (int)type_,
                                          min_frames_, base_ + from_frame, dPhi_, dV_, (float*)dWl_, nstream()));
     } else {
-      check_abi(btk_zelinski_process(Yo, Uo, Eo, 1, (int)K, (int)N, T_, Tn, alpha_, (int)type_ & 3, min_frames_, base_ + from_frame,
-                                     dPhi_, (float*)dPsi_, (float*)dWl_, nstream()));
+      check_abi(btk_zelinski_process(Yo, Uo, Eo, 1, (int)K, (int)N, T_, Tn, alpha_, ((int)type_ & 15) | BTK_PF_MCCOWAN_RULES, min_frames_,
+                                     base_ + from_frame, dPhi_, (float*)dPsi_, (float*)dWl_, nstream()));
     }
   }
   Yhost_valid_ = false;

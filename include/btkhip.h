@@ -248,9 +248,13 @@ int  btk_zelinski_process(void* Y, const void* C, const float* E, int S, int K, 
  * :620-632).  btk_pf_coherence_coeffs turns it (with threshold_of_Rij_) into the pair-weight matrices Cs (clean PSD)
  * and Cv (noise PSD, may be NULL for McCowan), complex64 [K][N][N].  btk_bf_apply_stats2 = btk_bf_apply plus, from
  * the same snapshots, the per-frame quadratic forms U (and V) complex64 [S][K][T_stride] and E (as btk_bf_apply_stats).
- *   McCowan:      btk_zelinski_process(Y, U, E, ...) -- the gain formula is Zelinski's with the weighted sum.
+ *   McCowan:      btk_zelinski_process(Y, U, E, ..., type | BTK_PF_MCCOWAN_RULES, ...) -- the gain formula is Zelinski's with the
+ *                 weighted sum; with the flag Re or |.| follows type & 1 in every frame, frames below min_frames included
+ *                 (:827-832), and the gain is applied to every frame >= min_frames whatever the type (:889-894), so that
+ *                 type = 0, 4, 8 or 12 filters as the reference does.
  *   Lefkimmiatis: btk_lefkimmiatis_process(Y, U, V, lambda, fbinX1, ...), lambda [dev] complex64 [K] = d^H pinv(R) d
  *                 from btk_mvdr_lambda (Cholesky with the identity fallback of :975-977), state u/v complex64 [S][K]. */
+#define BTK_PF_MCCOWAN_RULES 0x10
 int  btk_pf_coherence_coeffs(const void* R, float threshold, int K, int N, void* Cs, void* Cv, void* stream);
 int  btk_bf_apply_stats2(const void* W, const void* D, int per_stream_weights, const void* X, void* Y,
                          const void* Cs, const void* Cv, void* U, void* V, float* E,

@@ -357,3 +357,44 @@ def test_moving_look_direction_through_cpp_nodes(orc, dev, proto256, kinect_pcm,
     mv = np.concatenate(mv)
     nb = (b_switch + 1) * D
     assert mv.shape == stat.shape and np.array_equal(mv[:nb], stat[:nb]) and np.max(np.abs(mv[nb:] - stat[nb:])) > 5.0
+
+
+def test_mccowan_with_type_zelinski2_alone_applies_its_gain_through_cpp_nodes(orc, dev, proto256, kinect_pcm, tmp_path):
+    """type = 8 (TYPE_ZELINSKI2 alone, type & 3 == 0): McCowanPostFilter applies its |.| gain in every frame with
+    frame_no_ >= min_frames whatever the type (postfilter.cc:827-834, 882-894); only Zelinski's type 0 means `no filter`."""
+    import wave
+    from distant_speech_recognition_amd import btk20cpp as B
+    from distant_speech_recognition_amd.pybeamformer import calc_delays
+    M, m, r, D, FS = 256, 4, 1, 128, 16000
+    MPOS = [[-113.0, 0.0, 2.0], [36.0, 0.0, 2.0], [76.0, 0.0, 2.0], [113.0, 0.0, 2.0]]
+    h, g = proto256
+    L = 20000
+    afbs = []
+    for c in range(4):
+        p = str(tmp_path / ("t%d.wav" % c))
+        w = wave.open(p, "wb")
+        w.setnchannels(1); w.setsampwidth(2); w.setframerate(FS)
+        w.writeframes(kinect_pcm[c][:L].astype(np.int16).tobytes())
+        w.close()
+        sf = B.SampleFeaturePtr(block_len=D, shift_len=D, pad_zeros=True)
+        sf.read(p, FS)
+        afbs.append(B.OverSampledDFTAnalysisBankPtr(sf, prototype=h, M=M, m=m, r=r, delay_compensation_type=2))
+    bf = B.SubbandDSPtr(fftlen=M)
+    for a in afbs:
+        bf.set_channel(a)
+    pf = B.McCowanPostFilterPtr(bf, M, 0.7, 8)
+    pf.set_diffuse_noise_model(MPOS, FS, 343740.0)
+    pf.set_all_diagonal_loading(0.01)
+    pf.set_beamformer(bf)
+    sfb = B.OverSampledDFTSynthesisBankPtr(pf, prototype=g, M=M, m=m, r=r, delay_compensation_type=2)
+    delays = calc_delays("linear", MPOS, [-1.306379, None, None])
+    bf.calc_array_manifold_vectors(FS, delays)
+    out = np.concatenate([np.array(v) for v in sfb])
+    X = np.stack([orc.analysis(h, M, m, r, 2, kinect_pcm[c][:L]) for c in range(4)], axis=1)
+    wq = orc.calc_mainlobe(M, 4, FS, delays)
+    Y = orc.gsc_frames(X, wq, np.zeros_like(wq))
+    R = orc.diagonal_loading(orc.diffuse_noise_model(np.array(MPOS), M, FS), M, 0.01)
+    Yf, Wf = orc.mccowan_frames(X, Y, wq, R, alpha=0.7, type_=8)
+    ref = orc.synthesis(g, M, m, r, 2, Yf)
+    assert out.shape == ref.shape and np.max(np.abs(out - ref)) < 0.5           # <= 0.5 LSB at int16 scale
+    assert np.max(np.abs(orc.synthesis(g, M, m, r, 2, Y) - ref)) > 5.0           # the gain is visible in the expectation itself
