@@ -29,6 +29,7 @@ BTK_ERR_ALLOCATION = -3
 BTK_ERR_PARAMETER = -4
 BTK_ERR_HIP = -5
 BTK_ERR_NUMERIC = -6
+BTK_AEC_FRAME_CONTINUE = -(1 << 30)  # frame_no0 of btk_aec_process: count up from the state's frames done
 BTK_PF_MCCOWAN_RULES = 0x10      # type bit of btk_zelinski_process (include/btkhip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
@@ -71,6 +72,10 @@ SIGNATURES = {
     "btk_rls_process": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _l, _l, _vp, _vp, _vp, _vp, _vp]),
     "btk_rls_init_nc": (_i, [_i, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp]),
     "btk_rls_process_nc": (_i, [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _l, _l, _vp, _vp, _vp, _vp, _vp]),
+    "btk_aec_max_filter_length": (_i, []),
+    "btk_aec_dtd_state_in_lds": (_i, [_i, _i]),
+    "btk_aec_init": (_i, [_i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "btk_aec_process": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp]),
     "btk_bf_apply_stats": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _vp]),
     "btk_zelinski_process": (_i, [_vp, _vp, _vp, _i, _i, _i, _l, _l, _d, _i, _i, _l, _vp, _vp, _vp, _vp]),
     "btk_pf_coherence_coeffs": (_i, [_vp, _f, _i, _i, _vp, _vp, _vp]),

@@ -152,9 +152,13 @@ SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _m
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
 ZelinskiPostFilter, McCowanPostFilter, LefkimmiatisPostFilter = _mod.ZelinskiPostFilterPtr, _mod.McCowanPostFilterPtr, _mod.LefkimmiatisPostFilterPtr
 DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA = _mod.DOAEstimatorSRPBasePtr, _mod.DOAEstimatorSRPDSBLAPtr
+NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature = _mod.NLMSAcousticEchoCancellationFeaturePtr, _mod.KalmanFilterEchoCancellationFeaturePtr
+BlockKalmanFilterEchoCancellationFeature = _mod.BlockKalmanFilterEchoCancellationFeaturePtr
+DTDBlockKalmanFilterEchoCancellationFeature = _mod.DTDBlockKalmanFilterEchoCancellationFeaturePtr
 
 __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TYPE_APAB", "TYPE_ZELINSKI2", "NO_USE_POST_FILTER",
             "jarithmetic_error", "jinitialization_error", "jkey_error", "jparse_error", "jtype_error", "jiterator_error", "calc_all_delays",
             "SampleFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SubbandDS", "SubbandGSC", "SubbandGSCRLS",
             "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
-            "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA"]
+            "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
+            "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature"]

@@ -742,6 +742,93 @@ def rls_state_to_reference(mode, P, w, B):
     return np.conj(B.T) @ P @ B, np.conj(B.T) @ w      # P = B Pz B^H, wl = B wa
 
 
+# ---------------------------------------------------------------------------- subband acoustic echo cancellation
+AEC_KINDS = {"nlms": 0, "kalman_filter": 1, "block_kalman_filter": 2, "dtd_block_kalman_filter": 3}
+# the reference constructors' defaults (aec/aec.h:36,73,106,308)
+AEC_DEFAULTS = (
+    dict(delta=100.0, epsilon=1.0e-4, threshold=100.0),
+    dict(beta=0.95, sigma2=100.0, threshold=100.0),
+    dict(beta=0.95, sigmau2=10e-4, sigmak2=5.0, threshold=100.0, amp4play=1.0),
+    dict(beta=0.95, sigmau2=10e-4, sigmak2=5.0, snr_threshold=2.0, energy_threshold=100.0, smooth=0.9, amp4play=1.0),
+)
+
+
+class AECState:
+    """Device-resident state of S independent subband echo cancellers (aec/aec.cc), bins 0..M/2 only.
+    kind 0 NLMS, 1 Kalman, 2 block Kalman, 3 double-talk detecting block Kalman (or the names of AEC_KINDS); P = sample_num.
+    R complex128 [S][K][P], K complex128 [S][K][P][P], sigma2_v float64 [S][K], history complex128 [S][K][P] (slot 0 newest, scaled
+    by amp4play), dtd float64 [S][4] = {EkEnergy_, SkEnergy_, snr_, frames done}."""
+
+    def __init__(self, kind, S, M, P=1, device="cuda", **kw):
+        kind = AEC_KINDS.get(kind, kind)
+        if kind not in (0, 1, 2, 3):
+            raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "AECState: kind must be 0..3 or one of %s" % sorted(AEC_KINDS))
+        self.kind = kind
+        self.p = dict(AEC_DEFAULTS[kind])
+        unknown = set(kw) - set(self.p)
+        if unknown:
+            raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "AECState: unknown parameters %s" % sorted(unknown))
+        self.p.update(kw)
+        L = _lib.lib()
+        self.S, self.M, self.P, self.Kb = int(S), int(M), int(P), M // 2 + 1
+        dev = torch.device(device)
+        if min(self.S, self.M, self.P) < 1:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "AECState: S=%d M=%d sample_num=%d" % (S, M, P))
+        # (the limits -- filter length, number of subbands, P = 1 for the one-tap kinds -- are btk_aec_init's to refuse)
+        self.R = torch.empty((S, self.Kb, P), dtype=torch.complex128, device=dev)
+        self.K = torch.empty((S, self.Kb, P, P), dtype=torch.complex128, device=dev)
+        self.sigma2_v = torch.empty((S, self.Kb), dtype=torch.float64, device=dev)
+        self.history = torch.empty((S, self.Kb, P), dtype=torch.complex128, device=dev)
+        self.dtd = torch.empty((S, 4), dtype=torch.float64, device=dev)
+        check(L.btk_aec_init(self.kind, _np_ptr(self.params_array()), self.S, self.M, self.P, _ptr(self.R), _ptr(self.K),
+                             _ptr(self.sigma2_v), _ptr(self.history), _ptr(self.dtd), _stream()))
+
+    def params_array(self):
+        p = self.p
+        if self.kind == 0:
+            return np.array([p["delta"], p["epsilon"], 0, p["threshold"], 0, 0, 1, 0], np.float64)
+        if self.kind == 1:
+            return np.array([p["beta"], p["sigma2"], 0, p["threshold"], 0, 0, 1, 0], np.float64)
+        if self.kind == 2:
+            return np.array([p["beta"], p["sigmau2"], p["sigmak2"], p["threshold"], 0, 0, p["amp4play"], 0], np.float64)
+        return np.array([p["beta"], p["sigmau2"], p["sigmak2"], p["snr_threshold"], p["energy_threshold"], p["smooth"],
+                         p["amp4play"], 0], np.float64)
+
+    def reset(self):
+        """The nodes' reset() (aec.h:41,78,111-114): kinds 0 and 1 zero the filter and nothing else (kind 1 keeps sigma2_v and K);
+        kinds 2 and 3 reset their sources only, so all of the adaptive state and the played history survive."""
+        if self.kind < 2:
+            self.R.zero_()
+
+    def dtd_state_in_lds(self):
+        return bool(_lib.lib().btk_aec_dtd_state_in_lds(self.M, self.P))
+
+
+def aec_process(V, A, state, out=None, frame_no0=None, adapted=None):
+    """Echo canceller over a block: played V, recorded A complex64 [S][K][T] (rows may be padded) -> residual E [S][K][T]; state
+    updated in place.  frame_no0 (kind 3): None counts the frames up from the state's frames done (explicit frame numbers 0, 1, ...),
+    an int >= 0 counts up from it, a negative int is handed to every frame (a consumer that calls next(-5), aec.cc:902).
+    adapted: optional uint8 tensor laid out like E, set to 1 where the update ran."""
+    ts = _check(V, "V", torch.complex64, (state.S, state.Kb, None), rows=True)
+    S, K, T = V.shape
+    if _check(A, "A", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "aec_process: V and A must share one row stride")
+    if out is None:
+        out = rows_like(V, (S, K, T))
+    elif _check(out, "out", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "aec_process: out must share the row stride of V")
+    if adapted is not None and _check(adapted, "adapted", torch.uint8, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "aec_process: adapted must share the row stride of V")
+    fn0 = _lib.BTK_AEC_FRAME_CONTINUE if frame_no0 is None else int(frame_no0)
+    if frame_no0 is not None and fn0 <= _lib.BTK_AEC_FRAME_CONTINUE:
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "aec_process: frame_no0 out of range")
+    check(_lib.lib().btk_aec_process(state.kind, _np_ptr(state.params_array()), _ptr(V), _ptr(A), _ptr(out),
+                                     None if adapted is None else _ptr(adapted), S, state.M, state.P, ts, T, fn0,
+                                     _ptr(state.R), _ptr(state.K), _ptr(state.sigma2_v), _ptr(state.history), _ptr(state.dtd),
+                                     _stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------- Zelinski post-filter
 class ZelinskiState:
     """Summed CSD / PSD state of S post-filters (the part of BeamformerWeights::CSDs_/wp1_,

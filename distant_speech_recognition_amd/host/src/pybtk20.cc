@@ -18,6 +18,7 @@
 
 #include "beamformer/beamformer.h"
 #include "dereverberation/dereverberation.h"
+#include "aec/aec.h"
 #include "feature/feature.h"
 #include "modulated/modulated.h"
 #include "postfilter/postfilter.h"
@@ -681,4 +682,50 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("reset_filter", &SingleChannelWPEDereverberationFeature::reset_filter)
       .def("next_speaker", &SingleChannelWPEDereverberationFeature::next_speaker)
       .def("print_objective_func", &SingleChannelWPEDereverberationFeature::print_objective_func);
+
+  // ---- aec/aec.h (keyword names: aec/aec.i; the NLMS node calls its sources `original` and `distorted`)
+  py::class_<AcousticEchoCancellationNode_, VectorComplexFeatureStream, cref<AcousticEchoCancellationNode_>>(m, "AcousticEchoCancellationNode")
+      .def("set_block_frames", &AcousticEchoCancellationNode_::set_block_frames, py::arg("n"))
+      .def("block_frames", &AcousticEchoCancellationNode_::block_frames)
+      .def("sample_num", &AcousticEchoCancellationNode_::sample_num)
+      .def("block", [](AcousticEchoCancellationNode_& n) { return block_of(n); })
+      .def("filter_coefficients", [](AcousticEchoCancellationNode_& n, unsigned fbinX) {
+             const std::vector<double> r = n.filter_coefficients(fbinX);
+             py::array_t<std::complex<double>> a((py::ssize_t)(r.size() / 2));
+             memcpy(static_cast<void*>(a.mutable_data()), r.data(), sizeof(double) * r.size());
+             return a;
+           }, py::arg("fbinX"))
+      .def("state_covariance", [](AcousticEchoCancellationNode_& n, unsigned fbinX) {
+             const std::vector<double> r = n.state_covariance(fbinX);
+             const py::ssize_t P = (py::ssize_t)n.sample_num();
+             py::array_t<std::complex<double>> a({P, P});
+             memcpy(static_cast<void*>(a.mutable_data()), r.data(), sizeof(double) * r.size());
+             return a;
+           }, py::arg("fbinX"))
+      .def("observation_noise_variance", &AcousticEchoCancellationNode_::observation_noise_variance, py::arg("fbinX"));
+  py::class_<NLMSAcousticEchoCancellationFeature, AcousticEchoCancellationNode_, cref<NLMSAcousticEchoCancellationFeature>>(m, "NLMSAcousticEchoCancellationFeaturePtr")
+      .def(py::init([](py::object original, py::object distorted, double delta, double epsilon, double threshold, const std::string& nm) {
+             return new NLMSAcousticEchoCancellationFeature(as_cstream(original), as_cstream(distorted), delta, epsilon, threshold, nm);
+           }), py::arg("original"), py::arg("distorted"), py::arg("delta") = 100.0, py::arg("epsilon") = 1.0E-04, py::arg("threshold") = 100.0,
+           py::arg("nm") = "AEC");
+  py::class_<KalmanFilterEchoCancellationFeature, AcousticEchoCancellationNode_, cref<KalmanFilterEchoCancellationFeature>>(m, "KalmanFilterEchoCancellationFeaturePtr")
+      .def(py::init([](py::object played, py::object recorded, double beta, double sigma2, double threshold, const std::string& nm) {
+             return new KalmanFilterEchoCancellationFeature(as_cstream(played), as_cstream(recorded), beta, sigma2, threshold, nm);
+           }), py::arg("played"), py::arg("recorded"), py::arg("beta") = 0.95, py::arg("sigma2") = 100.0, py::arg("threshold") = 100.0,
+           py::arg("nm") = "KFEchoCanceller");
+  py::class_<BlockKalmanFilterEchoCancellationFeature, AcousticEchoCancellationNode_, cref<BlockKalmanFilterEchoCancellationFeature>>(m, "BlockKalmanFilterEchoCancellationFeaturePtr")
+      .def(py::init([](py::object played, py::object recorded, unsigned sample_num, double beta, double sigmau2, double sigmak2, double threshold,
+                       double amp4play, const std::string& nm) {
+             return new BlockKalmanFilterEchoCancellationFeature(as_cstream(played), as_cstream(recorded), sample_num, beta, sigmau2, sigmak2, threshold,
+                                                                 amp4play, nm);
+           }), py::arg("played"), py::arg("recorded"), py::arg("sample_num") = 1, py::arg("beta") = 0.95, py::arg("sigmau2") = 10e-4,
+           py::arg("sigmak2") = 5.0, py::arg("threshold") = 100.0, py::arg("amp4play") = 1.0, py::arg("nm") = "BlockKFEchoCanceller");
+  py::class_<DTDBlockKalmanFilterEchoCancellationFeature, BlockKalmanFilterEchoCancellationFeature, cref<DTDBlockKalmanFilterEchoCancellationFeature>>(m, "DTDBlockKalmanFilterEchoCancellationFeaturePtr")
+      .def(py::init([](py::object played, py::object recorded, unsigned sample_num, double beta, double sigmau2, double sigmak2, double snr_threshold,
+                       double energy_threshold, double smooth, double amp4play, const std::string& nm) {
+             return new DTDBlockKalmanFilterEchoCancellationFeature(as_cstream(played), as_cstream(recorded), sample_num, beta, sigmau2, sigmak2,
+                                                                    snr_threshold, energy_threshold, smooth, amp4play, nm);
+           }), py::arg("played"), py::arg("recorded"), py::arg("sample_num") = 1, py::arg("beta") = 0.95, py::arg("sigmau2") = 10e-4,
+           py::arg("sigmak2") = 5.0, py::arg("snr_threshold") = 2.0, py::arg("energy_threshold") = 100.0, py::arg("smooth") = 0.9,
+           py::arg("amp4play") = 1.0, py::arg("nm") = "DTDBlockKFEchoCanceller");
 }

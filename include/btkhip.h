@@ -221,6 +221,43 @@ int  btk_rls_process_nc(int mode, const double* params, const void* v, int per_s
                         const void* X, void* Y, int S, int M, int N, long T_stride, long T,
                         void* P_state, void* w_state, double* stream_state, void* workspace, void* stream);
 
+/* ---- Subband acoustic echo cancellation (float64 recursion) -----------------------------------
+ * Replaces the next() of the four canceller nodes of aec/aec.cc, per (stream, bin <= M/2) over a block of T frames:
+ *   kind 0  NLMSAcousticEchoCancellationFeature          (aec/aec.cc:34-80)    P = 1
+ *   kind 1  KalmanFilterEchoCancellationFeature          (aec/aec.cc:85-165)   P = 1
+ *   kind 2  BlockKalmanFilterEchoCancellationFeature     (aec/aec.cc:172-307)  P = sample_num
+ *   kind 3  DTDBlockKalmanFilterEchoCancellationFeature  (aec/aec.cc:801-942)  P = sample_num
+ * params [host] 8 doubles:
+ *   kind 0: delta, epsilon, -, threshold                                              (aec.h:36)
+ *   kind 1: beta, sigma2, -, threshold                                                (aec.h:73)
+ *   kind 2: beta, sigmau2, sigmak2, threshold, -, -, amp4play                         (aec.h:106)
+ *   kind 3: beta, sigmau2, sigmak2, snr_threshold, energy_threshold, smooth, amp4play (aec.h:308; the base class's
+ *           threshold_ is snr_threshold, aec.cc:805)
+ * V (played), A (recorded) [dev] complex64 [S][K][T_stride], K = M/2+1; E [dev] complex64 [S][K][T_stride] = A - R^T v
+ * (zdotu, no conjugate; bins above M/2 are the caller's mirror E[M-m] = conj(E[m])).  adapted [dev] uint8 [S][K][T_stride] or
+ * NULL: 1 where the frame's update ran (kinds 0-2: |v_0|^2 > threshold after amp4play, strict; kind 3: sf >= 0).
+ * State [dev], caller-owned, updated in place so that consecutive blocks continue bit for bit:
+ *   R_state   complex128 [S][K][P]     filter (filterCoefficient_)
+ *   K_state   complex128 [S][K][P][P]  state error covariance K_k_ (kind 1: the scalar in the real part; kind 0: unused)
+ *   sigma2_v  float64    [S][K]        observation noise variance (kinds 1-3)
+ *   history   complex128 [S][K][P]     ComplexBuffer_ (aec.h:117-191): slot 0 the newest played frame, scaled by amp4play
+ *   dtd_state float64    [S][4]        {EkEnergy_, SkEnergy_, snr_, frames done}; the first three are shared by all bins of a
+ *                                      stream and walked in bin order (update_band_, aec.cc:821-853)
+ * btk_aec_init writes the constructors' values: R = 0, history = 0, dtd_state = 0; kind 1: sigma2_v = K = sigma2 (aec.cc:95-98);
+ * kinds 2, 3: sigma2_v = sigmau2, K = sigmak2 I (aec.cc:190-203).
+ * frame_no0: the frame_no argument update_band_ receives (kind 3 only, aec.cc:902): >= 0 the block's frames count up from it;
+ * < 0 every frame of the block gets this value (a synthesis bank's next(-5)); BTK_AEC_FRAME_CONTINUE counts up from the state's
+ * frames done.  Limits: 1 <= P <= btk_aec_max_filter_length() (64), M <= 2048.  btk_aec_dtd_state_in_lds: 1 when kind 3 keeps K
+ * in LDS for the block ((M/2+1) P^2 16 B beside the per-bin vectors), 0 when it updates the exported state in place.           */
+#define BTK_AEC_FRAME_CONTINUE (-1073741824L)
+int  btk_aec_max_filter_length(void);
+int  btk_aec_dtd_state_in_lds(int M, int P);
+int  btk_aec_init(int kind, const double* params, int S, int M, int P, void* R_state, void* K_state, double* sigma2_v,
+                  void* history, double* dtd_state, void* stream);
+int  btk_aec_process(int kind, const double* params, const void* V, const void* A, void* E, void* adapted, int S, int M, int P,
+                     long T_stride, long T, long frame_no0, void* R_state, void* K_state, double* sigma2_v, void* history,
+                     double* dtd_state, void* stream);
+
 /* ---- Zelinski post-filter -------------------------------------------------------------------
  * Replaces ZelinskiFilter_f / ZelinskiFilter / ZelinskiPostFilter::next
  * (postfilter/postfilter.cc:57-219, 424-491).  Two calls per block:

@@ -13,11 +13,13 @@ import sys
 
 REF = "/root/reference/btk20_src"
 FILES = ["feature/feature.i", "modulated/modulated.i", "beamformer/beamformer.i", "postfilter/postfilter.i",
-         "dereverberation/dereverberation.i", "stream/stream.i"]
+         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i"]
 CLASSES = ["SampleFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
            "SubbandBeamformer", "SubbandDS", "SubbandGSC", "SubbandGSCRLS", "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter",
            "McCowanPostFilter", "LefkimmiatisPostFilter", "MultiChannelWPEDereverberation", "MultiChannelWPEDereverberationFeature",
-           "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream"]
+           "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream",
+           "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature", "BlockKalmanFilterEchoCancellationFeature",
+           "DTDBlockKalmanFilterEchoCancellationFeature"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
 
 
