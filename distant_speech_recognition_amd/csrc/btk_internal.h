@@ -24,6 +24,7 @@ struct btk_switches_t {
   bool disable_analysis512, disable_synthesis512, disable_fast, disable_fused, nlms_v1, wpe_noskip, wpe_timing, syn_narrow, rls_packed, wpe_solve_panel, wpe_solve_reg, wpe_herk_blocks /* BTK_WPE_HERK_BLOCKS: the round-2 block HERK instead of the lag-product form */,
        wpe_predict_valu /* BTK_WPE_PREDICT_VALU: the vector prediction kernel instead of the matrix-core one */,
        wpe_lagprod_f32 /* BTK_WPE_LAGPROD_F32: the float32 matrix instruction in the lag-product kernel (round 4) instead of the float16-split form */;
+  bool fused512_new /* BTK_FUSED512_NEW=0: the M = 512 fused launch goes to analysis512_bfz_kernel (fb_analysis512.hip) instead of fused512_kernel (fb_fused512.hip) */;
   int wpe_lagprod_waves /* BTK_WPE_LAGPROD_WAVES: 4 = four wavefronts x one column block per task (A/B: 8.6 ms per stream) instead of two x two (7.3, the default) */;
   int mvdr_reg_min /* BTK_MVDR_REG_MIN: channel count from which the MVDR design runs on the register-resident solver (default 64) */, nlms_alt, fused_var /* -1: default */, pf_jb, pf_tpw /* 0: default */, pf_mfma_min /* channels from which the matrix-core statistics kernel runs */;
 };
@@ -88,6 +89,9 @@ int btk_analysis512_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples
                                int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
 int btk_synthesis512_try(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
                          long b0, long bcount, hipStream_t st);
+// fb_fused512.hip: the production form of the fused kernel (M = 512, m = 4, r = 1), edge tiles first; i16: pcm holds 16-bit samples
+int btk_fused512_try(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                     int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
 // fb_fast.hip: register-FFT kernels for M in {256,512,1024,2048}, m = 4
 int btk_fast_analysis_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
                           long T_stride, long t0, long tcount, hipStream_t st);

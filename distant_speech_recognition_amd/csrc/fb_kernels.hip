@@ -471,7 +471,8 @@ int btk_fb_analysis_bf(const btk_fb_t* fb, const float* pcm, long nsamples, long
   if (!nofuse) {
     if ((fuse512 || fusefast || big_bytes) && scratch_bytes < wt_bytes)
       return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: scratch too small (%ld < %ld)", scratch_bytes, wt_bytes);
-    int rc = btk_analysis512_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+    int rc = btk_fused512_try(fb, pcm, 0, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+    if (rc == 0) rc = btk_analysis512_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
     if (rc != 0) return rc > 0 ? BTK_OK : rc;
     if (big_bytes) {
       rc = btk_big_analysis_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
@@ -526,7 +527,8 @@ int btk_fb_analysis_bf_i16(const btk_fb_t* fb, const short* pcm, long nsamples, 
   const long need = btk_fb_analysis_bf_scratch_bytes(fb, S, N, per_stream_weights, tcount);
   if (scratch_bytes < need) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: scratch too small (%ld < %ld)", scratch_bytes, need);
   hipStream_t st = as_stream(stream);
-  int rc = btk_analysis512_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+  int rc = btk_fused512_try(fb, pcm, 1, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+  if (rc == 0) rc = btk_analysis512_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
   if (rc == 0) rc = btk_big_analysis_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
   if (rc == 0 && !btk_switches().disable_fast) rc = btk_fast_analysis_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
   if (rc == 0) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: geometry not covered");
