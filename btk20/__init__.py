@@ -1,7 +1,8 @@
 """`btk20` -- the reference's import name.  Scripts written for the reference (`from btk20.beamformer import *`,
 `import btk20.pybeamformer`) resolve to this repo's engine without edits: this package IS
 `distant_speech_recognition_amd.btk20` under the reference's name -- its sub-modules are registered here as the very same module
-objects (no second layer of re-exporting files), `btk20.pybeamformer` is `distant_speech_recognition_amd.pybeamformer`."""
+objects (no second layer of re-exporting files), `btk20.pybeamformer` is `distant_speech_recognition_amd.pybeamformer`, `btk20.pytdoa` is
+`distant_speech_recognition_amd.pytdoa`."""
 import importlib
 import sys
 
@@ -14,4 +15,6 @@ for _name in ("stream", "feature", "modulated", "beamformer", "postfilter", "der
     globals()[_name] = _mod
 pybeamformer = importlib.import_module("distant_speech_recognition_amd.pybeamformer")
 sys.modules[__name__ + ".pybeamformer"] = pybeamformer
+pytdoa = importlib.import_module("distant_speech_recognition_amd.pytdoa")
+sys.modules[__name__ + ".pytdoa"] = pytdoa
 del _name, _mod

@@ -30,6 +30,7 @@ BTK_ERR_PARAMETER = -4
 BTK_ERR_HIP = -5
 BTK_ERR_NUMERIC = -6
 BTK_AEC_FRAME_CONTINUE = -(1 << 30)  # frame_no0 of btk_aec_process: count up from the state's frames done
+BTK_TDOA_NO_PEAK = -(1 << 31)        # lag of btk_tdoa_gcc_peaks where a frame has no peak (include/btkhip.h)
 BTK_PF_MCCOWAN_RULES = 0x10      # type bit of btk_zelinski_process (include/btkhip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
@@ -145,6 +146,10 @@ SIGNATURES = {
     "btk_hos_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _vp, _vp, _vp, _vp]),
     "btk_hos_minimize": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _i, _i, _i, _i, _l, _l, _i, _d, _d, _i, _d,
                               _vp, _vp, _vp, _vp, _vp, _vp]),
+    # GCC-PHAT TDOA: HammingFeature + FFTFeature (feature/feature.cc:1177-1258), PHATFeature.next + TDOAFeature.next (lib/pytdoa.py:32-114)
+    "btk_tdoa_frames": (_l, [_l, _i]),
+    "btk_tdoa_spectra": (_i, [_vp, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "btk_tdoa_gcc_peaks": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -1,7 +1,7 @@
 """btk20.feature (feature/feature.i): the names of that reference module, resolved to the C++ node layer
 (distant_speech_recognition_amd.btk20cpp = host/libbtk20hip.so bound with pybind11)."""
 from ..btk20cpp import (  # noqa: F401
-    SampleFeaturePtr, SampleFeature,
+    SampleFeaturePtr, SampleFeature, HammingFeaturePtr, HammingFeature, FFTFeaturePtr, FFTFeature,
 )
 
-__all__ = ['SampleFeaturePtr', 'SampleFeature']
+__all__ = ['SampleFeaturePtr', 'SampleFeature', 'HammingFeaturePtr', 'HammingFeature', 'FFTFeaturePtr', 'FFTFeature']

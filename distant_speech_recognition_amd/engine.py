@@ -1553,3 +1553,61 @@ def hos_minimize(X, wuH, BmH, x0=None, Nc=1, alpha=0.01, beta=3.0, gamma=-1.0, n
                                       T, maxiter, float(o["gtol"]), float(o["mindelta"]), int(o["max_halvings"]),
                                       float(o["armijo_c1"]), _ptr(xo), _ptr(fo), _ptr(it), _ptr(tf), _ptr(th), _stream()))
     return HOSResult(xo, fo, it, tf, th)
+
+
+# ---- GCC-PHAT time delay of arrival (btk_tdoa_*): HammingFeature + FFTFeature, PHATFeature.next + TDOAFeature.next ------------
+TDOA_NO_PEAK = _lib.BTK_TDOA_NO_PEAK
+
+
+def tdoa_frames(nsamples, D):
+    """Frames of SampleFeature(block_len=D, shift_len=D, pad_zeros=True) over nsamples samples: ceil(nsamples / D)."""
+    return int(_lib.lib().btk_tdoa_frames(int(nsamples), int(D)))
+
+
+def tdoa_spectra(pcm, D, L, window=True):
+    """Hamming window (float64 product rounded to float32; window=False: none), zero padding to L and forward transform of every
+    D-sample frame (feature/feature.cc:1177-1258).  pcm float32 [S][C][len] -> (X complex64 [S][C][T][L/2+1], energy float32 [S][C][T]),
+    T = ceil(len / D), energy = 2 sum_k |X_k|^2 (lib/pytdoa.py:47)."""
+    _check(pcm, "pcm", torch.float32, 3)
+    S, Cn, n = pcm.shape
+    D, L = int(D), int(L)
+    T = max(-(-n // D), 0) if D > 0 else 0
+    X = torch.empty((S, Cn, T, max(L, 0) // 2 + 1), dtype=torch.complex64, device=pcm.device)
+    energy = torch.empty((S, Cn, T), dtype=torch.float32, device=pcm.device)
+    check(_lib.lib().btk_tdoa_spectra(_ptr(pcm), n, n, S, Cn, D, L, int(bool(window)), _ptr(X), _ptr(energy), _stream()))
+    return X, energy
+
+
+def tdoa_pairs(pairs, C_channels, device):
+    """The pair list as the int32 [P][2] device tensor btk_tdoa_gcc_peaks reads; a host list is range-checked here."""
+    if isinstance(pairs, torch.Tensor):
+        _check(pairs, "pairs", torch.int32, (None, 2))
+        return pairs
+    a = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    if a.shape[0] < 1 or a.min() < 0 or a.max() >= C_channels:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "pairs must name channels 0 .. %d and be at least one" % (C_channels - 1))
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def tdoa_gcc_peaks(X, energy, pairs, energy_threshold, want_gcc=False):
+    """Phase transform, inverse transform and peak search of every listed pair and frame (lib/pytdoa.py:32-54, 87-114).
+    X complex64 [S][C][T][L/2+1], energy float32 [S][C][T], pairs [P][2] -> (lag int32 [S][P][T], height float32 [S][P][T]
+    [, gcc float32 [S][P][T][L]]); lag is TDOA_NO_PEAK and height 0 where a frame has no peak."""
+    _check(X, "X", torch.complex64, 4)
+    S, Cn, T, K = X.shape
+    L = 2 * (K - 1)
+    _check(energy, "energy", torch.float32, (S, Cn, T))
+    pd = tdoa_pairs(pairs, Cn, X.device)
+    P = pd.shape[0]
+    lag = torch.empty((S, P, T), dtype=torch.int32, device=X.device)
+    height = torch.empty((S, P, T), dtype=torch.float32, device=X.device)
+    gcc = torch.empty((S, P, T, L), dtype=torch.float32, device=X.device) if want_gcc else None
+    check(_lib.lib().btk_tdoa_gcc_peaks(_ptr(X), _ptr(energy), _ptr(pd), P, float(energy_threshold), S, Cn, T, L, _ptr(lag),
+                                        _ptr(height), C.c_void_p(0) if gcc is None else _ptr(gcc), _stream()))
+    return (lag, height, gcc) if want_gcc else (lag, height)
+
+
+def tdoa_estimate(pcm, D, L, pairs, energy_threshold):
+    """tdoa_spectra then tdoa_gcc_peaks: pcm float32 [S][C][len] -> (lag int32 [S][P][T], height float32 [S][P][T])."""
+    X, energy = tdoa_spectra(pcm, D, L)
+    return tdoa_gcc_peaks(X, energy, pairs, energy_threshold)

@@ -74,3 +74,61 @@ class SampleFeature : public VectorFloatFeatureStream {
   unsigned long samples_gen_;
   void samples_changed_() { pcm16_state_ = 0; samples_gen_++; }
 };
+
+// HammingFeature (reference feature/feature.h:492-507, feature/feature.cc:1177-1200): the float64 window times the source's
+// block, stored as float32 -- that rounding is part of the reference.  Host arithmetic: it is the node boundary.
+class HammingFeature : public VectorFloatFeatureStream {
+ public:
+  HammingFeature(const VectorFloatFeatureStreamPtr& samp, const String& nm = "Hamming");
+  virtual ~HammingFeature() {}
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { samp_->reset(); VectorFloatFeatureStream::reset(); }
+  // engine hooks for a consumer that takes the blocks from the source in bulk (FFTFeature): the source node, and the state
+  // transitions of n next() calls whose last block was last_block (vector_ = its windowed form, as after next())
+  VectorFloatFeatureStreamPtr& source() { return samp_; }
+  void advance_blocks(long n, const float* last_block);
+ private:
+  VectorFloatFeatureStreamPtr samp_;
+  std::vector<double> window_;
+};
+typedef Inherit<HammingFeature, VectorFloatFeatureStreamPtr> HammingFeaturePtr;
+
+// FFTFeature (reference feature/feature.h:518-546, feature/feature.cc:1205-1258, :29-43): the source's block zero-padded to
+// fftLen, forward real transform, handed out as the full spectrum -- the half spectrum plus its conjugate mirror, bins 0 and
+// fftLen/2 real -- widened from the device's complex64 (btk_tdoa_spectra; fftLen a power of two from 256 to 16384, block
+// length <= fftLen: the library refuses the rest at the first next()).
+// Over a HammingFeature over a SampleFeature, the window and the transform of up to block_frames frames are one launch and the
+// frames are served one by one from a host copy; over any other source each next() uploads one frame (no window) and launches a
+// one-frame block.  block_frames: constructor argument, 0 = BTK_TDOA_BLOCK_FRAMES or 64.
+class FFTFeature : public VectorComplexFeatureStream {
+ public:
+  FFTFeature(const VectorFloatFeatureStreamPtr& samp, unsigned fftLen = 512, const String& nm = "FFT", long block_frames = 0);
+  virtual ~FFTFeature() {}
+  virtual const gsl_vector_complex* next(int frame_no = -5);
+  virtual void reset();
+  unsigned fftLen() const { return fftLen_; }
+  unsigned windowLen() const { return windowLen_; }
+  unsigned nBlocks() const { return 4; }
+  unsigned subsamplerate() const { return 2; }
+  unsigned subSampRate() { return subsamplerate(); }
+  long block_frames() const { return block_frames_; }
+  void set_block_frames(long n);
+  // engine hooks for a consumer that batches over channels (btk20.pytdoa): whether this node stands over a HammingFeature over
+  // a SampleFeature, and then up to nmax of the SampleFeature's un-windowed blocks back to back in dst (nmax * windowLen()
+  // floats) with the state transitions of as many next() calls on every node of the chain; fewer than nmax: the stream ended
+  bool has_sample_chain() const { return sample_ != NULL; }
+  long pull_sample_blocks(float* dst, long nmax);
+  // launches this node has made since it was built (tests)
+  long launches() const { return launches_; }
+ private:
+  void fill_block_();
+  void serve_(const float* half);
+  VectorFloatFeatureStreamPtr samp_;
+  HammingFeature* hamming_;      // samp_ when it is one over a SampleFeature, else NULL
+  SampleFeature* sample_;        // its source
+  unsigned fftLen_, windowLen_;
+  long block_frames_, blk_n_, blk_pos_, launches_;
+  PinnedBuffer h_in_, h_out_;
+  DeviceBuffer d_in_, d_out_, d_energy_;
+};
+typedef Inherit<FFTFeature, VectorComplexFeatureStreamPtr> FFTFeaturePtr;

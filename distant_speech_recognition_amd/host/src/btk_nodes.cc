@@ -3904,3 +3904,136 @@ bool SubbandGraphPool::is_end(unsigned g) const
   if (g >= graphs_.size()) throw jindex_error("SubbandGraphPool: graph %d of %d\n", (int)g, (int)graphs_.size());
   return !graphs_[g].live && graphs_[g].served >= graphs_[g].nblocks;
 }
+
+// ================================================================================ HammingFeature / FFTFeature (TDOA front end)
+HammingFeature::HammingFeature(const VectorFloatFeatureStreamPtr& samp, const String& nm)
+    : VectorFloatFeatureStream(samp->size(), nm), samp_(samp), window_(samp->size())
+{
+  const double temp = 2. * M_PI / (double)(size() - 1);              // feature.cc:1181-1183
+  for (unsigned i = 0; i < size(); i++) window_[i] = 0.54 - 0.46 * cos(temp * i);
+}
+
+const gsl_vector_float* HammingFeature::next(int frame_no)
+{
+  if (frame_no == frame_no_) return vector_;
+  if (frame_no >= 0 && frame_no - 1 != frame_no_)
+    throw jindex_error("Problem in Feature %s: %d != %d\n", name().c_str(), frame_no - 1, frame_no_);
+  const gsl_vector_float* block = samp_->next(frame_no_ + 1);
+  increment_();
+  for (unsigned i = 0; i < size(); i++) vector_->data[i] = (float)(window_[i] * (double)block->data[i]);
+  return vector_;
+}
+
+void HammingFeature::advance_blocks(long n, const float* last_block)
+{
+  if (n <= 0) return;
+  frame_no_ += (int)n;
+  for (unsigned i = 0; i < size(); i++) vector_->data[i] = (float)(window_[i] * (double)last_block[i]);
+}
+
+static long tdoa_default_block_frames()
+{
+  const char* e = getenv("BTK_TDOA_BLOCK_FRAMES");
+  const long v = (e && *e) ? atol(e) : 0;
+  return v > 0 ? v : 64;
+}
+
+FFTFeature::FFTFeature(const VectorFloatFeatureStreamPtr& samp, unsigned fftLen, const String& nm, long block_frames)
+    : VectorComplexFeatureStream(fftLen, nm), samp_(samp), hamming_(NULL), sample_(NULL), fftLen_(fftLen), windowLen_(samp->size()),
+      block_frames_(block_frames > 0 ? block_frames : tdoa_default_block_frames()), blk_n_(0), blk_pos_(0), launches_(0)
+{
+  if (fftLen < 2) throw jdimension_error("FFTFeature %s: fftLen %u\n", nm.c_str(), fftLen);
+  hamming_ = dynamic_cast<HammingFeature*>(samp_.operator->());
+  if (hamming_) sample_ = dynamic_cast<SampleFeature*>(hamming_->source().operator->());
+  // overlapping blocks (shiftLen != blockLen) are no frames of one signal: they go frame by frame
+  if (sample_ && sample_->shiftlen() != sample_->size()) sample_ = NULL;
+  if (!sample_) hamming_ = NULL;
+}
+
+void FFTFeature::set_block_frames(long n)
+{
+  block_frames_ = n > 0 ? n : tdoa_default_block_frames();
+}
+
+void FFTFeature::reset()
+{
+  samp_->reset();
+  VectorComplexFeatureStream::reset();
+  blk_n_ = blk_pos_ = 0;
+}
+
+long FFTFeature::pull_sample_blocks(float* dst, long nmax)
+{
+  if (!sample_) throw jconsistency_error("FFTFeature %s: not over a HammingFeature over a SampleFeature\n", name().c_str());
+  const long n = sample_->next_blocks(dst, nmax);
+  if (n > 0) hamming_->advance_blocks(n, dst + (size_t)(n - 1) * windowLen_);
+  frame_no_ += (int)n;
+  blk_n_ = blk_pos_ = 0;
+  if (n < nmax) is_end_ = true;
+  return n;
+}
+
+// one launch for the frames the source has next: a block of the sample chain with the window in the kernel, or the one frame
+// the source hands out, as it is
+void FFTFeature::fill_block_()
+{
+  const size_t D = windowLen_, K = fftLen_ / 2 + 1;
+  long n = 1;
+  int window = BTK_TDOA_WINDOW_NONE;
+  if (sample_) {
+    float* in = static_cast<float*>(h_in_.ensure(sizeof(float) * D * (size_t)block_frames_));
+    n = sample_->next_blocks(in, block_frames_);
+    if (n <= 0) { is_end_ = true; throw jiterator_error("end of samples!"); }
+    hamming_->advance_blocks(n, in + (size_t)(n - 1) * D);
+    window = BTK_TDOA_WINDOW_HAMMING;
+  } else {
+    const gsl_vector_float* block;
+    try {
+      block = samp_->next(frame_no_ + 1);
+    } catch (jiterator_error&) {
+      is_end_ = true;
+      throw;
+    }
+    float* in = static_cast<float*>(h_in_.ensure(sizeof(float) * D));
+    memcpy(in, block->data, sizeof(float) * D);
+  }
+  hipStream_t st = static_cast<hipStream_t>(btk_node_stream());
+  const size_t nin = D * (size_t)n, nout = 2 * K * (size_t)n;
+  float* din = static_cast<float*>(d_in_.ensure(sizeof(float) * nin));
+  void* dout = d_out_.ensure(sizeof(float) * nout);
+  void* den = d_energy_.ensure(sizeof(float) * (size_t)n);
+  float* out = static_cast<float*>(h_out_.ensure(sizeof(float) * nout));
+  check_hip(hipMemcpyAsync(din, h_in_.get(), sizeof(float) * nin, hipMemcpyHostToDevice, st), "FFTFeature upload");
+  check_abi(btk_tdoa_spectra(din, (long)nin, (long)nin, 1, 1, (int)D, (int)fftLen_, window, dout, den, st));
+  launches_++;
+  check_hip(hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, st), "FFTFeature download");
+  check_hip(hipStreamSynchronize(st), "FFTFeature block");
+  blk_n_ = n;
+  blk_pos_ = 0;
+}
+
+// unpack_half_complex (feature.cc:29-43) from the device's half spectrum
+void FFTFeature::serve_(const float* half)
+{
+  const unsigned L = fftLen_, L2 = L / 2;
+  double* v = vector_->data;
+  v[0] = half[0]; v[1] = 0.0;
+  v[2 * L2] = half[2 * L2]; v[2 * L2 + 1] = 0.0;
+  for (unsigned m = 1; m < L2; m++) {
+    const double re = half[2 * m], im = half[2 * m + 1];
+    v[2 * m] = re; v[2 * m + 1] = im;
+    v[2 * (L - m)] = re; v[2 * (L - m) + 1] = -im;
+  }
+}
+
+const gsl_vector_complex* FFTFeature::next(int frame_no)
+{
+  if (frame_no == frame_no_) return vector_;
+  if (frame_no >= 0 && frame_no - 1 != frame_no_)
+    throw jindex_error("Problem in Feature %s: %d != %d\n", name().c_str(), frame_no - 1, frame_no_);
+  if (blk_pos_ >= blk_n_) fill_block_();
+  serve_(static_cast<const float*>(h_out_.get()) + (size_t)blk_pos_ * 2 * (fftLen_ / 2 + 1));
+  blk_pos_++;
+  increment_();
+  return vector_;
+}

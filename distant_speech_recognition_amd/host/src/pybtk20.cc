@@ -316,6 +316,34 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("addWhiteNoise", &SampleFeature::addWhiteNoise, py::arg("snr"))
       .def("setSamples", [](SampleFeature& s, py::array_t<double, py::array::c_style | py::array::forcecast> a, unsigned sampleRate) {
              GslVec v(a); s.setSamples(v.v, sampleRate); }, py::arg("samples"), py::arg("sampleRate"));
+  // the TDOA front end (feature/feature.i:525-531, 567-573)
+  py::class_<HammingFeature, VectorFloatFeatureStream, cref<HammingFeature>>(m, "HammingFeaturePtr")
+      .def(py::init([](py::object samp, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             return new HammingFeature(sp, nm);
+           }), py::arg("samp"), py::arg("nm") = "Hamming");
+  py::class_<FFTFeature, VectorComplexFeatureStream, cref<FFTFeature>>(m, "FFTFeaturePtr")
+      .def(py::init([](py::object samp, unsigned fft_len, const std::string& nm, long block_frames) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             return new FFTFeature(sp, fft_len, nm, block_frames);
+           }), py::arg("samp"), py::arg("fft_len") = 512, py::arg("nm") = "FFT", py::arg("block_frames") = 0)
+      .def("fftLen", &FFTFeature::fftLen)
+      .def("windowLen", &FFTFeature::windowLen)
+      .def("nBlocks", &FFTFeature::nBlocks)
+      .def("subsamplerate", &FFTFeature::subsamplerate)
+      .def("subSampRate", &FFTFeature::subSampRate)
+      .def("set_block_frames", &FFTFeature::set_block_frames, py::arg("n"))
+      .def("block_frames", &FFTFeature::block_frames)
+      .def("launches", &FFTFeature::launches)
+      .def("has_sample_chain", &FFTFeature::has_sample_chain)
+      // up to nmax un-windowed sample blocks of the chain as float32 [n][windowLen] (a copy), every node of the chain advanced by n
+      .def("pull_sample_blocks", [](FFTFeature& f, long nmax) {
+             if (nmax < 0) nmax = 0;
+             std::vector<float> buf((size_t)nmax * f.windowLen());
+             const long n = f.pull_sample_blocks(buf.data(), nmax);
+             py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)f.windowLen()});
+             if (n > 0) memcpy(a.mutable_data(), buf.data(), sizeof(float) * (size_t)n * f.windowLen());
+             return a; }, py::arg("nmax"));
 
   // ---- modulated/modulated.h
   py::class_<OverSampledDFTAnalysisBank, VectorComplexFeatureStream, cref<OverSampledDFTAnalysisBank>>(m, "OverSampledDFTAnalysisBankPtr")

@@ -580,6 +580,31 @@ int  btk_hos_minimize(const void* X, const void* mask, const void* wuH, const vo
                       double mindelta, int max_halvings, double armijo_c1, void* x_out, void* f_out, void* iters_out,
                       void* trace_f, void* trace_halvings, void* stream);
 
+/* ---- GCC-PHAT time delay of arrival: the front end of unit_test/test_tdoa_estimator.py --------------------------------
+ * HammingFeature::next + FFTFeature::next (feature/feature.cc:1177-1200, :1205-1258, :29-43) for a block of frames of
+ * pcm [dev] float32 [S][C] rows of len samples, pcm_stride apart.  Frame t covers samples t D .. t D + D - 1, zero beyond len
+ * (pad_zeros); T = btk_tdoa_frames(len, D) = ceil(len / D).  window BTK_TDOA_WINDOW_HAMMING: 0.54 - 0.46 cos(2 pi i / (D - 1))
+ * and the product in float64, rounded to float32 (the gsl_vector_float of HammingFeature); BTK_TDOA_WINDOW_NONE: the frames as
+ * they are (FFTFeature over a source that is no HammingFeature).  Zero padding to L; forward transform, unnormalised.
+ *   X [dev] complex64 [S][C][T][L/2+1];  energy [dev] float32 [S][C][T] = 2 sum_{k <= L/2} |X_k|^2 (lib/pytdoa.py:47)
+ * L a power of two from 256 to 16384, 2 <= D <= L; BTK_ERR_DIMENSION otherwise, nothing launched.                          */
+#define BTK_TDOA_WINDOW_NONE 0
+#define BTK_TDOA_WINDOW_HAMMING 1
+long btk_tdoa_frames(long len, int D);
+int  btk_tdoa_spectra(const float* pcm, long len, long pcm_stride, int S, int C, int D, int L, int window, void* X,
+                      void* energy, void* stream);
+/* PHATFeature.next + TDOAFeature.next (lib/pytdoa.py:32-54, :87-114) for every listed pair and every frame:
+ *   pairs [dev] int32 [P][2] channel indices, in the caller's order ((b, a) is another pair than (a, b))
+ *   P_k = X_a[k] conj X_b[k] / |X_a[k] conj X_b[k]|, g = irfft(P) (1/L, imaginary parts of bins 0 and L/2 ignored)
+ *   lag [dev] int32 [S][P][T]: the first n with the largest |g[n]|, as n (n < L/2) or n - L;  height [dev] float32 = |g[n]|
+ *   gcc [dev] float32 [S][P][T][L] or NULL (the normal case): g itself.
+ * No peak -- lag BTK_TDOA_NO_PEAK, height 0 -- where both energies are <= energy_threshold (gcc row: zeros), where a bin of
+ * either channel is exactly zero (the reference's 0/0; gcc row: NaN), where g has no positive |g[n]|, and for a pair that
+ * names a channel outside 0 .. C-1.                                                                                        */
+#define BTK_TDOA_NO_PEAK (-2147483647 - 1)
+int  btk_tdoa_gcc_peaks(const void* X, const void* energy, const int* pairs, int P, float energy_threshold, int S, int C,
+                        long T, int L, void* lag, void* height, void* gcc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
