@@ -612,8 +612,9 @@ __device__ __forceinline__ void lagprod_task(const float2* __restrict__ Xk, cons
 // rate of v_mfma_f32_32x32x2_f32) with BOTH operands split into a high and a low float16 part, a = ah + al, b = bh + bl, and three
 // products ah bh + ah bl + al bh accumulated in float32: the dropped al bl term and the parts' own rounding are 2^-22 of |a| |b|, i.e.
 // the accuracy of the float32 instruction it replaces (one bin, 8 channels x 33 lags, 1000 frames against float64: max |R - R64| /
-// max |R64| 1.1e-7 for the split, 1.3e-7 for float32 products; filter taps 4.7e-6 vs 5.3e-6).  float16's range is met by one power-of-two
-// scale per (stream, bin) and operand (wpe_lp_scale_kernel: 2^14 / max, exact to undo).  48 matrix instructions of 32 cycles per 16 frames
+// max |R64| 1.1e-7 for the split, 1.3e-7 for float32 products; filter taps 4.7e-6 vs 5.3e-6).  float16's range is met by power-of-two
+// scales per (stream, bin): one per target channel for the weights, one for the products (wpe_lp_scale_kernel: 2^14 / max, exact to
+// undo).  48 matrix instructions of 32 cycles per 16 frames
 // of a task instead of 128 of 64.  The Hankel operand Wh[(l1, c)][u] = w_c(u + l1) needs 8 consecutive float16 values starting at ANY
 // index: the weight span of a tile is kept in LDS as its eight one-frame shifts, split, so that every read is one aligned 16-byte word.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -626,40 +627,51 @@ __device__ __forceinline__ f16x8 mk8(unsigned a, unsigned b, unsigned c, unsigne
   return __builtin_bit_cast(f16x8, v);
 }
 
-// scales[(s K + k) 2 + {0, 1}] = power of two that brings the largest weight / the bound 2 max|y|^2 of the products to < 2^14
+// scales[(s K + k) (C + 1) + c] = power of two that brings the largest weight of TARGET CHANNEL c to < 2^14, [.. + C] the same for the
+// bound 2 max|y|^2 of the products.  The weights get one scale per target channel, not one per bin: the rows of the weight operand
+// belong to one target channel each, so the scale leaves the product as a factor of the accumulator row and is undone at the store.
+// With one scale per bin a single frame of ONE channel near the 1e-3 floor (weight 1e6 -- a real-valued bin, DC or Nyquist, crossing
+// zero) pushed the ordinary weights (~ 1 / |y|^2) of the SEVEN OTHER channels of its tile under float16's smallest subnormal: those
+// channels' normal equations lost the tile's frames (taps 1.6e-2 of the largest off the float64 oracle at 8 channels x 14 lags, 300
+// frames, second iteration; float32 products: 5e-5).  Within a channel the same frame dominates that channel's own R by more than
+// float32 resolves, so nothing is lost there that float32 products would keep.
+constexpr int LP16_CMAX = 32;
 __global__ __launch_bounds__(256)
 void wpe_lp_scale_kernel(const float2* __restrict__ X, const float* __restrict__ Winv, WpeGeom g, float* __restrict__ scales,
                          int* __restrict__ tile_exp /* [S][K][nt_stride] */, int nt_stride)
 {
-  __shared__ float red[2][4];
-  __shared__ float sab[2];
+  __shared__ float red[4];
+  __shared__ float sac[LP16_CMAX + 1];                               // [C] weight scales, then the product scale
   const int k = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
-  float wm = 0.f, ym = 0.f;
-  if (bin_active(g, k)) {
-    for (int c = 0; c < g.C; c++) {
+  const bool act = bin_active(g, k);
+  float* sck = scales + ((long)s * g.K + k) * (g.C + 1);
+  // (clamped: a bin of near-silence must not drive 2^(14 - e) -- or 1 / (sa sb) at the store -- out of float32's range)
+  auto scale_of = [](float m) {
+    int e = 0;
+    if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &e);                 // m < 2^e
+    return ldexpf(1.f, 14 - e < -60 ? -60 : (14 - e > 60 ? 60 : 14 - e));
+  };
+  float ym = 0.f;
+  for (int c = 0; c <= g.C; c++) {                                   // c == C: the products
+    float m = ym;
+    if (act && c < g.C) {
       const float* w = Winv + (((long)s * g.C + c) * g.K + k) * g.T_stride;
       const float2* y = X + (((long)s * g.K + k) * g.C + c) * g.T_stride;
+      m = 0.f;
       for (long t = tid; t < g.T; t += 256) {
-        if (t >= g.lowerN) wm = fmaxf(wm, w[t]);
+        if (t >= g.lowerN) m = fmaxf(m, w[t]);
         const float2 v = y[t];
         ym = fmaxf(ym, fmaf(v.x, v.x, v.y * v.y));
       }
     }
-  }
-  for (int o = 32; o > 0; o >>= 1) { wm = fmaxf(wm, __shfl_xor(wm, o)); ym = fmaxf(ym, __shfl_xor(ym, o)); }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = wm; red[1][tid >> 6] = ym; }
-  __syncthreads();
-  if (tid == 0) {
-    wm = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    ym = 2.f * fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-    int ea = 0, eb = 0;
-    if (wm > 0.f && wm < 3.0e38f) (void)frexpf(wm, &ea);                     // wm < 2^ea
-    if (ym > 0.f && ym < 3.0e38f) (void)frexpf(ym, &eb);
-    // (clamped: a bin of near-silence must not drive 2^(14 - e) -- or 1 / (sa sb) at the store -- out of float32's range)
-    const int xa = 14 - ea < -60 ? -60 : (14 - ea > 60 ? 60 : 14 - ea), xb = 14 - eb < -60 ? -60 : (14 - eb > 60 ? 60 : 14 - eb);
-    scales[((long)s * g.K + k) * 2 + 0] = ldexpf(1.f, xa);
-    scales[((long)s * g.K + k) * 2 + 1] = ldexpf(1.f, xb);
-    sab[0] = ldexpf(1.f, xa); sab[1] = ldexpf(1.f, xb);
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    __syncthreads();                                                 // (red of the last channel has been read)
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+      m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+      sck[c] = sac[c] = scale_of(c < g.C ? m : 2.f * m);
+    }
   }
   __syncthreads();
   // Exponent balance per 64-frame tile (round 6; see lagprod16_task): half the distance between the exponents of the largest scaled
@@ -667,8 +679,8 @@ void wpe_lp_scale_kernel(const float2* __restrict__ X, const float* __restrict__
   // task; the weights' span starts la frames in and is LP_WT + RL nb - 1 long (nb = the task's row blocks, 1 .. LP_RMAX): one value per
   // (tile, q = (L - la) / RL, nb), the SAME numbers the tasks used to find themselves -- every tile, in the wavefronts that prepare the
   // operands, 52 tasks per bin at L = 33: 7 % of the kernel.  te[(j NLA + q) LP_RMAX + nb - 1].
-  if (!bin_active(g, k)) return;
-  const float sa = sab[0], sb = sab[1];
+  if (!act) return;
+  const float sb = sac[g.C];
   const int RLs = 32 / g.C, NLA = (g.L + RLs - 1) / RLs + 1;
   const long ntile = (g.T + LP_WT - 1) / LP_WT;
   int* te = tile_exp + ((long)s * g.K + k) * nt_stride;
@@ -685,8 +697,8 @@ void wpe_lp_scale_kernel(const float2* __restrict__ X, const float* __restrict__
     if (in_lds)
       for (long i = tid; i < tB - tA; i += 256) {
         float m = 0.f;
-        for (int c = 0; c < g.C; c++) m = fmaxf(m, Winv[(((long)s * g.C + c) * g.K + k) * g.T_stride + tA + i]);
-        wmx[i] = m;
+        for (int c = 0; c < g.C; c++) m = fmaxf(m, Winv[(((long)s * g.C + c) * g.K + k) * g.T_stride + tA + i] * sac[c]);
+        wmx[i] = m;                                                  // the largest SCALED weight of the frame
       }
     __syncthreads();
     const long j = j0 + (tid >> 4);
@@ -717,11 +729,11 @@ void wpe_lp_scale_kernel(const float2* __restrict__ X, const float* __restrict__
           } else {
             for (int c = 0; c < g.C; c++) {
               const float* w = Winv + (((long)s * g.C + c) * g.K + k) * g.T_stride;
-              for (long tt = lo; tt < hi; tt++) wmq = fmaxf(wmq, w[tt]);
+              for (long tt = lo; tt < hi; tt++) wmq = fmaxf(wmq, w[tt] * sac[c]);
             }
           }
           t = hi > t ? hi : t;                                       // the next, longer span adds only its tail
-          const float wm2 = wmq * sa;
+          const float wm2 = wmq;
           int ea = 0, eb = 0;
           if (wm2 > 0.f && bm2 > 0.f) { (void)frexpf(wm2, &ea); (void)frexpf(bm2, &eb); }
           te[(j * NLA + q) * LP_RMAX + nbk - 1] = (ea - eb) >> 1;    // |e| <= 64: exact powers of two
@@ -806,7 +818,7 @@ __device__ __forceinline__ f16x8 lp16_block(const u32x12& w)
 template <int C, int NR, int NCW>
 __device__ __forceinline__ void lagprod16_task(const float2* __restrict__ Xk, const float* __restrict__ Wk, const WpeGeom& g, float2* __restrict__ R,
                                                int ys_ld, int d, int la, int s, int k, float2* ys, uint4* wcp,
-                                               float sa, float sb, const int* __restrict__ te)
+                                               const float* __restrict__ sck /* [C] weight scales, product scale */, const int* __restrict__ te)
 {
   // Columns (round 6): the 2 C^2 = 128 columns are (re | im) x 64 channel pairs; a wavefront's column blocks are the REAL and the
   // IMAGINARY parts of the same 32 pairs (NCW = 2: pairs 32 wv + m; NCW = 1: pairs 32 (wv >> 1) + m, part wv & 1), so both blocks form
@@ -824,6 +836,10 @@ __device__ __forceinline__ void lagprod16_task(const float2* __restrict__ Xk, co
   float2* ysq = ys + C * ys_ld;                                    // the second factors, scaled: [C][yq_ld]
   float2 ypf[C];
   float wpf[C];
+  float sa[C];                                                     // (wave-uniform: scalar registers)
+#pragma unroll
+  for (int c = 0; c < C; c++) sa[c] = sck[c];
+  const float sb = sck[C];
   int ehpf = 0;
   bool yok = false, wok = false;                                   // the prefetched sample / weight of this thread lies inside the recording
   const int teq = ((L + RL - 1) / RL + 1) * LP_RMAX, teo = ((L - la) / RL) * LP_RMAX + NR - 1;
@@ -920,7 +936,7 @@ __device__ __forceinline__ void lagprod16_task(const float2* __restrict__ Xk, co
         unsigned short* wch = reinterpret_cast<unsigned short*>(wcp);
 #pragma unroll
         for (int c = 0; c < C; c += 2) {
-          const float w0 = wl ? (wpf[c] * sa) * fa : 0.f, w1 = wl ? (wpf[c + 1] * sa) * fa : 0.f;
+          const float w0 = wl ? (wpf[c] * sa[c]) * fa : 0.f, w1 = wl ? (wpf[c + 1] * sa[c + 1]) * fa : 0.f;
           const unsigned hi = pk_hi(w0, w1);
           const unsigned lo = pk_hi(sub_h_lo(w0, hi), sub_h_hi(w1, hi));
 #pragma unroll
@@ -991,19 +1007,20 @@ __device__ __forceinline__ void lagprod16_task(const float2* __restrict__ Xk, co
   // out of the segment loop and held in ~80 registers across the tile loop, which spilled the accumulators)
   int ms = pairl, lks = lk;
   asm volatile("" : "+v"(ms), "+v"(lks));
-  const float unscale = 1.0f / (sa * sb);
   float2* Rc[4];
+  float unscale[4];                                                // per row: the target channel's weight scale and the product scale
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const int c = i + 4 * lks;                                     // row % C for row = i + 8 (r >> 2) + 4 lk
     Rc[i] = R + (((long)s * C + c) * g.K + k) * (long)P * P;
+    unscale[i] = 1.0f / (sck[c] * sb);
   }
   {
     const int c1 = ms / C, c2 = ms % C;
     const bool lower = c1 >= c2;
     const bool skip = (d == 0 && c1 < c2);                         // the swapped pair stores this entry
     const long off0 = lower ? (long)c1 * L * P + (long)c2 * L - d : ((long)c2 * L - d) * P + (long)c1 * L;
-    const float sre = unscale, sim = lower ? unscale : -unscale;   // (the upper triangle holds the conjugate)
+    const float sgn = lower ? 1.f : -1.f;                          // (the upper triangle holds the conjugate)
 #pragma unroll
     for (int j = 0; j < NR; j++) {
 #pragma unroll
@@ -1017,13 +1034,13 @@ __device__ __forceinline__ void lagprod16_task(const float2* __restrict__ Xk, co
 #endif
         float2* dst = &Rc[reg & 3][off0 + (long)l1 * (P + 1)];
         if constexpr (NCW == 2) {                                  // both parts of the entry are this lane's: one 8-byte store
-          const float2 v = make_float2(sre * acc[j][0][reg], sim * acc[j][1][reg]);
+          const float2 v = make_float2(unscale[reg & 3] * acc[j][0][reg], sgn * unscale[reg & 3] * acc[j][1][reg]);
           if (seg0 > 0) { const float2 o = *dst; *dst = make_float2(o.x + v.x, o.y + v.y); }
           else *dst = v;
           acc[j][0][reg] = 0.f; acc[j][1][reg] = 0.f;
         } else {
           float* dp = reinterpret_cast<float*>(dst) + (imw ? 1 : 0);
-          const float v = (imw ? sim : sre) * acc[j][0][reg];
+          const float v = (imw ? sgn * unscale[reg & 3] : unscale[reg & 3]) * acc[j][0][reg];
           *dp = seg0 > 0 ? *dp + v : v;
           acc[j][0][reg] = 0.f;
         }
@@ -1070,13 +1087,13 @@ __device__ __forceinline__ void wpe_lagprod16_body(const float2* __restrict__ X,
   const int la = L - RL * (first + nb);
   const float2* Xk = X + ((long)s * g.K + k) * C * g.T_stride;
   const float* Wk = Winv + ((long)s * C * g.K + k) * g.T_stride;
-  const float sa = scales[((long)s * g.K + k) * 2], sb = scales[((long)s * g.K + k) * 2 + 1];
+  const float* sck = scales + ((long)s * g.K + k) * (C + 1);
   const int* te = tile_exp + ((long)s * g.K + k) * nt_stride;
   switch (nb) {
-    case 4: lagprod16_task<C, 4, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sa, sb, te); break;
-    case 3: lagprod16_task<C, 3, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sa, sb, te); break;
-    case 2: lagprod16_task<C, 2, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sa, sb, te); break;
-    default: lagprod16_task<C, 1, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sa, sb, te); break;
+    case 4: lagprod16_task<C, 4, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sck, te); break;
+    case 3: lagprod16_task<C, 3, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sck, te); break;
+    case 2: lagprod16_task<C, 2, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sck, te); break;
+    default: lagprod16_task<C, 1, NCW>(Xk, Wk, g, R, ys_ld, d, la, s, k, ys, wcp, sck, te); break;
   }
 }
 
@@ -1303,7 +1320,7 @@ long btk_wpe_workspace_bytes(int S, int K, int C, int lowerN, int upperN, long T
 {
   const long P = (long)C * (upperN - lowerN + 1);
   const long nb = (long)S * C * K;
-  return nb * P * P * 8 + nb * P * 8 + nb * T_stride * 4 + (long)S * K * 8 + (long)S * K * (T_stride / 64 + 2) * (((upperN - lowerN + 1) + 32 / (C > 0 && C <= 32 ? C : 32) - 1) / (32 / (C > 0 && C <= 32 ? C : 32)) + 1) * 4 * 4 + 256;
+  return nb * P * P * 8 + nb * P * 8 + nb * T_stride * 4 + (long)S * K * (C + 1) * 4 + (long)S * K * (T_stride / 64 + 2) * (((upperN - lowerN + 1) + 32 / (C > 0 && C <= 32 ? C : 32) - 1) / (32 / (C > 0 && C <= 32 ? C : 32)) + 1) * 4 * 4 + 256;
 }
 
 int btk_wpe_estimate(const void* X, int S, int K, int C, long T_stride, long T, int lowerN, int upperN, int iterations,
@@ -1321,10 +1338,10 @@ int btk_wpe_estimate(const void* X, int S, int K, int C, long T_stride, long T, 
   float2* R = static_cast<float2*>(workspace);
   float2* rvec = R + nb * P * P;
   float* Winv = reinterpret_cast<float*>(rvec + nb * P);
-  float* lp_scales = Winv + nb * T_stride;                          // [S][K][2]: operand scales of the float16 lag-product kernel
+  float* lp_scales = Winv + nb * T_stride;                          // [S][K][C + 1]: operand scales of the float16 lag-product kernel
   const int nla = C <= 32 ? ((g.L + 32 / C - 1) / (32 / C) + 1) : 1;
   const int nt_stride = (int)(T_stride / 64 + 2) * nla * 4;          // per (stream, bin): [tiles][q][row blocks] (wpe_lp_scale_kernel)
-  int* lp_tile_exp = reinterpret_cast<int*>(lp_scales + (long)S * K * 2);   // [S][K][nt_stride]: its per-tile exponent trades
+  int* lp_tile_exp = reinterpret_cast<int*>(lp_scales + (long)S * K * (C + 1));   // [S][K][nt_stride]: its per-tile exponent trades
   const float2* Xp = static_cast<const float2*>(X);
   float2* Gp = static_cast<float2*>(G);
   const int ntile = (int)((P + 63) / 64);
