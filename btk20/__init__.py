@@ -2,7 +2,7 @@
 `import btk20.pybeamformer`) resolve to this repo's engine without edits: this package IS
 `distant_speech_recognition_amd.btk20` under the reference's name -- its sub-modules are registered here as the very same module
 objects (no second layer of re-exporting files), `btk20.pybeamformer` is `distant_speech_recognition_amd.pybeamformer`, `btk20.pytdoa` is
-`distant_speech_recognition_amd.pytdoa`."""
+`distant_speech_recognition_amd.pytdoa`, `btk20.pykalman` is `distant_speech_recognition_amd.pykalman`."""
 import importlib
 import sys
 
@@ -17,4 +17,6 @@ pybeamformer = importlib.import_module("distant_speech_recognition_amd.pybeamfor
 sys.modules[__name__ + ".pybeamformer"] = pybeamformer
 pytdoa = importlib.import_module("distant_speech_recognition_amd.pytdoa")
 sys.modules[__name__ + ".pytdoa"] = pytdoa
+pykalman = importlib.import_module("distant_speech_recognition_amd.pykalman")
+sys.modules[__name__ + ".pykalman"] = pykalman
 del _name, _mod

@@ -150,7 +150,17 @@ SIGNATURES = {
     "btk_tdoa_frames": (_l, [_l, _i]),
     "btk_tdoa_spectra": (_i, [_vp, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "btk_tdoa_gcc_peaks": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
+    # EKF / IEKF tracking over the TDOA peaks: ExtendedKalmanFilter.next, KalmanFilter.update, IteratedExtendedKalmanFilter.update
+    # (lib/pykalman.py:84-162, :199-266); the first argument points to an EkfParams
+    "btk_ekf_track": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp, _vp]),
 }
+
+
+class EkfParams(C.Structure):
+    """btk_ekf_params of include/btkhip.h, field by field."""
+    _fields_ = [("n", _i), ("model", _i), ("type", _i), ("F", _d * 9), ("U", _d * 9), ("sigmaV2", _d), ("time_delta", _d),
+                ("gate_prob", _d), ("num_iterations", _i), ("iteration_threshold", _d), ("threshold", _d), ("minimum_pairs", _i),
+                ("Ts", _d), ("c", _d)]
 
 
 def lib():

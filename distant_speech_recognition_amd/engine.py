@@ -1611,3 +1611,69 @@ def tdoa_estimate(pcm, D, L, pairs, energy_threshold):
     """tdoa_spectra then tdoa_gcc_peaks: pcm float32 [S][C][len] -> (lag int32 [S][P][T], height float32 [S][P][T])."""
     X, energy = tdoa_spectra(pcm, D, L)
     return tdoa_gcc_peaks(X, energy, pairs, energy_threshold)
+
+
+# ---- EKF / IEKF speaker tracking over the TDOA peaks (btk_ekf_track): lib/pykalman.py over lib/pytdoa.py's observation models ----
+EKF_TRACKED, EKF_OBSERVED, EKF_UPDATED, EKF_ROUNDS_SHIFT = 1, 2, 4, 8
+EKF_MODELS = {"linear": 0, "circular": 1, "cartesian": 2}          # state length 1, 2, 3
+EKF_TYPES = {"ekf": 0, "iekf": 1}
+
+
+def ekf_params(model, type, F, U, sigmaV2, time_delta, gate_prob=0.0, num_iterations=3, iteration_threshold=1e-4, threshold=0.12,
+               minimum_pairs=2, Ts=1.0 / 16000, c=343000.0):
+    """The parameter record of btk_ekf_track.  model 'linear' | 'circular' | 'cartesian', type 'ekf' | 'iekf', F and U n x n with
+    n the model's state length (1, 2, 3)."""
+    F, U = np.asarray(F, np.float64), np.asarray(U, np.float64)
+    n = F.shape[0] if F.ndim == 2 else -1
+    if model not in EKF_MODELS or type not in EKF_TYPES:
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "ekf_params: model %r, type %r" % (model, type))
+    if n != EKF_MODELS[model] + 1 or F.shape != (n, n) or U.shape != (n, n):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "ekf_params: F %s and U %s must be %d x %d for the %s model" % (
+            F.shape, U.shape, EKF_MODELS[model] + 1, EKF_MODELS[model] + 1, model))
+    p = _lib.EkfParams()
+    p.n, p.model, p.type = n, EKF_MODELS[model], EKF_TYPES[type]
+    F3, U3 = np.zeros((3, 3)), np.zeros((3, 3))
+    F3[:n, :n], U3[:n, :n] = F, U
+    p.F[:], p.U[:] = F3.ravel().tolist(), U3.ravel().tolist()
+    p.sigmaV2, p.time_delta, p.gate_prob = float(sigmaV2), float(time_delta), float(gate_prob)
+    p.num_iterations, p.iteration_threshold = int(num_iterations), float(iteration_threshold)
+    p.threshold, p.minimum_pairs, p.Ts, p.c = float(threshold), int(minimum_pairs), float(Ts), float(c)
+    return p
+
+
+def ekf_state(x, K, time, device, streams=1, last_update=-1):
+    """The float64 [S][16] state record of btk_ekf_track: x, K_filter (3 x 3 row-major, leading n x n block), time, lastUpdateT."""
+    x, K = np.asarray(x, np.float64).ravel(), np.asarray(K, np.float64)
+    n = len(x)
+    rec = np.zeros(16)
+    rec[:n] = x
+    K3 = np.zeros((3, 3))
+    K3[:n, :n] = K
+    rec[3:12] = K3.ravel()
+    rec[12], rec[13] = time, last_update
+    return torch.from_numpy(np.tile(rec, (int(streams), 1))).to(device)
+
+
+def ekf_track(lag, height, geom, params, state, t_begin=None):
+    """Track S independent streams through the T frames of a block of TDOA peaks, in one launch.
+    lag int32 [S][P][T], height float32 [S][P][T] (tdoa_gcc_peaks), geom float64 [P][6] (the model's per-pair geometry),
+    params an ekf_params record, state float64 [S][16] (ekf_state; updated in place, so the next block continues),
+    t_begin int32 [S] or None: the stream's first tracked frame.
+    -> (xk float64 [S][T][3], Kf float64 [S][T][9], flags int32 [S][T]): xk_filter, K_filter and EKF_TRACKED | EKF_OBSERVED |
+    EKF_UPDATED | rounds << EKF_ROUNDS_SHIFT after every frame."""
+    if not isinstance(params, _lib.EkfParams):
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "ekf_track: params must come from ekf_params")
+    _check(lag, "lag", torch.int32, 3)
+    S, P, T = lag.shape
+    _check(height, "height", torch.float32, (S, P, T))
+    _check(geom, "geom", torch.float64, (P, 6))
+    _check(state, "state", torch.float64, (S, 16))
+    if t_begin is not None:
+        _check(t_begin, "t_begin", torch.int32, (S,))
+    xk = torch.empty((S, T, 3), dtype=torch.float64, device=lag.device)
+    Kf = torch.empty((S, T, 9), dtype=torch.float64, device=lag.device)
+    flags = torch.empty((S, T), dtype=torch.int32, device=lag.device)
+    check(_lib.lib().btk_ekf_track(C.cast(C.pointer(params), C.c_void_p), _ptr(lag), _ptr(height), _ptr(geom),
+                                   C.c_void_p(0) if t_begin is None else _ptr(t_begin), S, P, T, _ptr(state), _ptr(xk), _ptr(Kf),
+                                   _ptr(flags), _stream()))
+    return xk, Kf, flags

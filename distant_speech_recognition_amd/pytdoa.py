@@ -52,6 +52,7 @@ class _PairEngine:
         self.block_frames = int(block_frames) if block_frames else (self.channels[0].block_frames() if self.batched else 1)
         self.launch_count = 0
         self._pairs_dev = None
+        self.block_serial = 0    # counts the blocks computed
         self._clear()
 
     def _nodes_ok(self):
@@ -64,6 +65,7 @@ class _PairEngine:
         self.base = 0            # frame number of the block's first frame
         self.n = 0               # frames in the block
         self.X = self.energy = self.lag = self.height = None
+        self.lag_dev = self.height_dev = None      # the block's peaks on the device, int32 / float32 [1][P][n]: what a tracker reads
 
     def reset(self):
         for c in self.channels:
@@ -104,6 +106,8 @@ class _PairEngine:
         lag, height = eng.tdoa_gcc_peaks(self.X, self.energy, self._pairs_dev, self.threshold)
         self.launch_count += 1
         self.lag, self.height = lag.cpu().numpy()[0], height.cpu().numpy()[0]
+        self.lag_dev, self.height_dev = lag, height
+        self.block_serial += 1
         self.base, self.n = frame_no, n
 
     def seek(self, frame_no):
@@ -247,6 +251,7 @@ class TDOAFeatureVector:
         self._threshold = threshold
         self._c = c
         self._tdoabuf = {}
+        self._tdoa_frame = None
         self._engine = None
         self.reset()
 
@@ -292,7 +297,7 @@ class TDOAFeatureVector:
             buf.setdefault(src.first_micx, {})[src.second_micx] = delay
             if height > self._threshold:
                 observations.append(MicrophonePairObservation(src.pairx, src.first_micx, src.second_micx, delay))
-        self._tdoabuf = buf
+        self._tdoabuf, self._tdoa_frame = buf, None
         return observations if len(observations) >= self._minimum_pairs else None
 
     def instantaneous_position(self, frame_no):
@@ -300,7 +305,28 @@ class TDOAFeatureVector:
         pass
 
     def mic_pair_tdoa(self):
+        if self._tdoa_frame is not None:                 # a frame a tracker served from the device: the table is built on demand
+            buf = {}
+            for src, delay, _ in self._peaks(self._tdoa_frame):
+                buf.setdefault(src.first_micx, {})[src.second_micx] = delay
+            self._tdoabuf, self._tdoa_frame = buf, None
         return self._tdoabuf
+
+    def _defer_tdoa(self, frame_no):
+        """frame_no is the frame mic_pair_tdoa() is about (the engine's current one), without a next(frame_no) having run."""
+        self._tdoa_frame = frame_no
+
+    def _pair_geometry(self, row):
+        """float64 [P][6]: row(pair source) -> up to six numbers per pair."""
+        g = numpy.zeros((len(self._mic_pair_srcs), 6), numpy.float64)
+        for p, src in enumerate(self._mic_pair_srcs):
+            r = numpy.ravel(row(src))
+            g[p, :len(r)] = r
+        return g
+
+    def _track_model(self):
+        """(model name, per-pair geometry [P][6]) of engine.ekf_track: the two microphone positions."""
+        return "cartesian", self._pair_geometry(lambda s: numpy.concatenate([self._mpos[s.first_micx][:3], self._mpos[s.second_micx][:3]]))
 
     def __iter__(self):
         while True:
@@ -351,6 +377,9 @@ class FarfieldLinearArrayTDOAFeatureVector(TDOAFeatureVector):
     def _baseline(self, pair):
         return self._mpos[pair.second_micx] - self._mpos[pair.first_micx]
 
+    def _track_model(self):
+        return "linear", self._pair_geometry(self._baseline)
+
     def tdoa(self, mic_pair, azimuth):
         return numpy.array([self._baseline(mic_pair) * numpy.cos(azimuth) / self._c], numpy.float64)
 
@@ -393,6 +422,9 @@ class FarfieldCircularArrayTDOAFeatureVector(TDOAFeatureVector):
 
     def _offset(self, pair):
         return self._mpos[pair.second_micx] - self._mpos[pair.first_micx]
+
+    def _track_model(self):
+        return "circular", self._pair_geometry(lambda s: self._offset(s)[:3])
 
     def tdoa(self, mic_pair, polarX):
         theta, phi = polarX[0], polarX[1]

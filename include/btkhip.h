@@ -605,6 +605,50 @@ int  btk_tdoa_spectra(const float* pcm, long len, long pcm_stride, int S, int C,
 int  btk_tdoa_gcc_peaks(const void* X, const void* energy, const int* pairs, int P, float energy_threshold, int S, int C,
                         long T, int L, void* lag, void* height, void* gcc, void* stream);
 
+/* ---- EKF / IEKF speaker tracking: the tracker of unit_test/test_source_tracking.py -------------------------------------------
+ * ExtendedKalmanFilter.next / KalmanFilter.update / IteratedExtendedKalmanFilter.update (lib/pykalman.py:84-162, :199-216,
+ * :232-266) over TDOAFeatureVector.next and the tdoa / linearize / calc_linearized_observation of the three feature vectors
+ * (lib/pytdoa.py:213-287, :365-415, :460-516), for S independent streams and the T frames of a block, float64 throughout:
+ *   lag [dev] int32 [S][P][T], height [dev] float32 [S][P][T]: the outputs of btk_tdoa_gcc_peaks.  A pair is observed in a
+ *     frame where (double)height > threshold and lag != BTK_TDOA_NO_PEAK; its delay is (double)lag * Ts.  A frame with fewer
+ *     than minimum_pairs observed pairs leaves the state as it is.
+ *   geom [dev] float64 [P][6] per pair (first, second microphone), shared by the streams:
+ *     BTK_EKF_MODEL_LINEAR    (n = 1, azimuth):          [d_second - d_first, ...] distances from the first microphone
+ *     BTK_EKF_MODEL_CIRCULAR  (n = 2, polar, azimuth):   [p_second - p_first (3), ...]
+ *     BTK_EKF_MODEL_CARTESIAN (n = 3, position):         [p_first (3), p_second (3)]
+ *   t_begin [dev] int32 [S] or NULL (all 0): the stream's first tracked frame of the block; earlier frames get flags 0.
+ *   state [dev] float64 [S][16], read and written: x[3], K_filter[9] (row-major 3 x 3, the leading n x n block is used), time,
+ *     lastUpdateT, two spare.  time is the reference's counter at the first tracked frame (set_time), lastUpdateT is -1 before
+ *     the first update.  T frames in one call and in consecutive calls give the same bits.
+ *   xk [dev] float64 [S][T][3], Kf [dev] float64 [S][T][9]: xk_filter and K_filter after every frame.
+ *   flags [dev] int32 [S][T]: BTK_EKF_TRACKED | BTK_EKF_OBSERVED | BTK_EKF_UPDATED (observed and not gated) | rounds of the
+ *     IEKF used << BTK_EKF_ROUNDS_SHIFT.
+ * The gate is the reference's scipy.stats.chi.cdf(d2, nobs) > gate_prob with d2 the SQUARED Mahalanobis distance (gate_prob 0:
+ * no gate).  The nobs x nobs inverse is replaced by the n x n one of sigmaV2 I + H^T H K_predict.
+ * BTK_ERR_PARAMETER for a parameter outside its range, BTK_ERR_DIMENSION for S, P, T < 1 or P > 877; nothing is launched.  */
+#define BTK_EKF_MODEL_LINEAR 0
+#define BTK_EKF_MODEL_CIRCULAR 1
+#define BTK_EKF_MODEL_CARTESIAN 2
+#define BTK_EKF_TYPE_EKF 0
+#define BTK_EKF_TYPE_IEKF 1
+#define BTK_EKF_TRACKED 1
+#define BTK_EKF_OBSERVED 2
+#define BTK_EKF_UPDATED 4
+#define BTK_EKF_ROUNDS_SHIFT 8
+#define BTK_EKF_MAX_ROUNDS 1000000
+typedef struct btk_ekf_params {
+  int n, model, type;          /* state length, BTK_EKF_MODEL_*, BTK_EKF_TYPE_* */
+  double F[9], U[9];           /* state transition, process noise covariance: row-major 3 x 3, leading n x n block used */
+  double sigmaV2, time_delta, gate_prob;
+  int num_iterations;          /* IEKF rounds at most (>= 1) */
+  double iteration_threshold;  /* the IEKF stops after the round with |eta_i - eta_(i-1)|^2 below it */
+  double threshold;            /* peak height above which a pair is observed */
+  int minimum_pairs;
+  double Ts, c;                /* sampling period in seconds; speed of sound in position units per second */
+} btk_ekf_params;
+int  btk_ekf_track(const btk_ekf_params* params, const void* lag, const void* height, const void* geom, const void* t_begin,
+                   int S, int P, long T, void* state, void* xk, void* Kf, void* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
