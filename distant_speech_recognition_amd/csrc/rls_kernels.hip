@@ -211,9 +211,11 @@ void rls_bin_kernel(const float2* __restrict__ X, const zd* __restrict__ V /* [S
   for (long t0 = 0; t0 < T; t0 += RTB, buf ^= 1) {
     if (t0 + RTB < T) prefetch(t0 + RTB);
     const int nt = (T - t0 < RTB) ? (int)(T - t0) : RTB;
+    bool tile_adapted = false;                             // (workgroup-uniform, like `adapt`)
     for (int tt = 0; tt < nt; tt++) {
       // WG-uniform: every bin of the workgroup walks through the same barriers; `commit` masks the state change
       const bool adapt = (p.mode == 0) ? (p.update != 0) : (ctrl[(long)s * T + t0 + tt] != 0.f);
+      tile_adapted |= adapt;
       const bool commit = (p.mode == 1) || k > 0;                            // beamformer.cc:1589 starts at bin 1
       zd xs[W];
 #pragma unroll
@@ -354,7 +356,8 @@ void rls_bin_kernel(const float2* __restrict__ X, const zd* __restrict__ V /* [S
     // n^H P = 0 for ever; in floating point the component along n is multiplied by 1/mu per frame (nothing in the
     // recursion damps it), so it is removed before it can matter.  (The reference cannot leak: it works in N-1
     // dimensions.)  P -= (P v) v^H/|v|^2 + v (v^H P)/|v|^2 - v (v^H P v) v^H/|v|^4, v = vs (mode 1) / conj(wq) (mode 0)
-    {
+    // A tile of held frames (silence gate, update off) has not changed P: nothing to remove, and the state stays bit for bit.
+    if (tile_adapted) {
       zd pa = zmk(0.0, 0.0), pb = zmk(0.0, 0.0);
 #pragma unroll
       for (int q = 0; q < W; q++) {
@@ -610,8 +613,10 @@ void rls_packed_kernel(const float2* __restrict__ X, const zd* __restrict__ V, i
     if (nbuf == 2) { if (t0 + rtb < T) stage(buf ^ 1, t0 + rtb); }      // the other buffer: last read a tile ago
     else { stage(0, t0); __syncthreads(); }                                 // one buffer: the previous tile ended with a barrier
     const int nt = (T - t0 < rtb) ? (int)(T - t0) : rtb;
+    bool tile_adapted = false;                             // (workgroup-uniform, like `adapt`)
     for (int tt = 0; tt < nt; tt++) {
       const bool adapt = (p.mode == 0) ? (p.update != 0) : (ctrl[(long)s * T + t0 + tt] != 0.f);
+      tile_adapted |= adapt;
       for (int n = tid; n < N; n += NT) { const float2 xf = L.xt[(buf * N + n) * rld + tt]; L.xv[n] = zmk((double)xf.x, (double)xf.y); }
       __syncthreads();
       // Yc = v^H x, canceller output with the current weights, |v - w|^2 (mode 0 normalisation)
@@ -705,8 +710,9 @@ void rls_packed_kernel(const float2* __restrict__ X, const zd* __restrict__ V, i
     }
     if (tid < nt) Y[sk * T_stride + t0 + tid] = yout[tid];
     // ---- once per tile: P <- Q P Q, Q = I - n n^H for every blocked direction n (v / |v| resp. conj(wq) / |wq|, then the c_j):
-    // in exact arithmetic P n = 0 for ever; in floating point that component is multiplied by 1 / mu per frame
-    for (int d = 0; d < NC; d++) {
+    // in exact arithmetic P n = 0 for ever; in floating point that component is multiplied by 1 / mu per frame.  A tile of held
+    // frames (silence gate, update off) has not changed P: nothing to remove, and the state stays bit for bit.
+    for (int d = 0; tile_adapted && d < NC; d++) {
       for (int n = tid; n < N; n += NT) {
         L.xv[n] = (d == 0) ? zscale(L.dv[n], sqrt(inv_vv)) : L.cx[(d - 1) * N + n];
       }

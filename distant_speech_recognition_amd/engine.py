@@ -716,12 +716,14 @@ class RLSState:
 
 def rls_process(X, state, out=None):
     """RLS canceller over a block: X complex64 [S][K][N][T] -> Y [S][K][T]; state updated in place."""
-    _need_cuda(X, "X")
+    _check(X, "X", torch.complex64, 4)
     S, K, N, T = X.shape
     if (S, K, N) != (state.S, state.K, state.N):
         raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "rls_process: shapes do not match the state")
     if out is None:
         out = torch.empty((S, K, T), dtype=torch.complex64, device=X.device)
+    else:
+        _check(out, "Y", torch.complex64, (S, K, T))
     params = state.params_array()
     ws = state.workspace(T)
     check(_lib.lib().btk_rls_process_nc(state.mode, _np_ptr(params), _ptr(state.v), state.per_stream,
