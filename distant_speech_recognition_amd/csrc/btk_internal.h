@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include "btkhip.h"
+#include "fb_route.h"
 
 struct btk_fb {
   int M, m, r, R, D, K;
@@ -18,15 +19,14 @@ struct btk_fb {
 
 int btk_set_error(int code, const char* fmt, ...);
 
-// Diagnostic A/B switches of the profiling scripts (profiles/): read from the environment ONCE per process, in one place, so
-// that sizing and dispatch can never disagree; production runs leave them unset.
-struct btk_switches_t {
-  bool disable_analysis512, disable_synthesis512, disable_fast, disable_fused, nlms_v1, wpe_noskip, wpe_timing, syn_narrow, rls_packed, wpe_solve_panel, wpe_solve_reg, wpe_herk_blocks /* BTK_WPE_HERK_BLOCKS: the round-2 block HERK instead of the lag-product form */,
+// Diagnostic A/B switches of the profiling scripts (profiles/): read from the environment ONCE per process, in one place;
+// production runs leave them unset.  (The ones that decide filter-bank coverage are the base, which fb_route.h turns into routes.)
+struct btk_switches_t : fb_switches {
+  bool nlms_v1, wpe_noskip, wpe_timing, rls_packed, wpe_solve_panel, wpe_solve_reg, wpe_herk_blocks /* BTK_WPE_HERK_BLOCKS: the round-2 block HERK instead of the lag-product form */,
        wpe_predict_valu /* BTK_WPE_PREDICT_VALU: the vector prediction kernel instead of the matrix-core one */,
        wpe_lagprod_f32 /* BTK_WPE_LAGPROD_F32: the float32 matrix instruction in the lag-product kernel (round 4) instead of the float16-split form */;
-  bool fused512_new /* BTK_FUSED512_NEW=0: the M = 512 fused launch goes to analysis512_bfz_kernel (fb_analysis512.hip) instead of fused512_kernel (fb_fused512.hip) */;
   int wpe_lagprod_waves /* BTK_WPE_LAGPROD_WAVES: 4 = four wavefronts x one column block per task (A/B: 8.6 ms per stream) instead of two x two (7.3, the default) */;
-  int mvdr_reg_min /* BTK_MVDR_REG_MIN: channel count from which the MVDR design runs on the register-resident solver (default 64) */, nlms_alt, fused_var /* -1: default */, pf_jb, pf_tpw /* 0: default */, pf_mfma_min /* channels from which the matrix-core statistics kernel runs */;
+  int mvdr_reg_min /* BTK_MVDR_REG_MIN: channel count from which the MVDR design runs on the register-resident solver (default 64) */, nlms_alt, pf_jb, pf_tpw /* 0: default */, pf_mfma_min /* channels from which the matrix-core statistics kernel runs */;
 };
 const btk_switches_t& btk_switches();
 
@@ -78,7 +78,10 @@ constexpr int BTK_RSRC_I16X2_SSCALED = 0x0002B02C;
 __device__ btk_f4v btk_buffer_load_i16x4_f32(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.ptr.buffer.load.format.v4f32");
 constexpr int BTK_RSRC_I16X4_SSCALED = 0x00063FAC;
 
-// fb_analysis512.hip: specialised analysis kernel (M=512, m=4); returns 1 handled / 0 not covered / <0 error
+// What covers a plan is decided by fb_route.h, which fb_kernels.hip asks; the launchers below are called for the routes they
+// implement and return BTK_OK or an error (another geometry is an error).  pcm with i16: 16-bit samples, else float.
+// fb_analysis512.hip (M = 512, m = 4, r <= 2; pinned byte for byte by the benchmark's records, hence the older protocol and one
+// function per sample type): 1 launched / 0 not this file's geometry / < 0 error
 int btk_analysis512_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
                         long T_stride, long t0, long tcount, hipStream_t st);
 int btk_analysis512_bf_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
@@ -89,23 +92,16 @@ int btk_analysis512_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples
                                int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
 int btk_synthesis512_try(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
                          long b0, long bcount, hipStream_t st);
-// fb_fused512.hip: the production form of the fused kernel (M = 512, m = 4, r = 1), edge tiles first; i16: pcm holds 16-bit samples
-int btk_fused512_try(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
-                     int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
-// fb_fast.hip: register-FFT kernels for M in {256,512,1024,2048}, m = 4
-int btk_fast_analysis_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
-                          long T_stride, long t0, long tcount, hipStream_t st);
-int btk_fast_analysis_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
-                              long T_stride, long t0, long tcount, hipStream_t st);
-int btk_fast_analysis_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                                 int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
-int btk_fast_analysis_bf_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                             int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
-// fb_fused_big.hip: fused analysis -> fixed-weight beamformer for M = 1024 / 2048 (m = 4, r = 1); scratch bytes 0 = geometry not covered
-long btk_big_analysis_bf_scratch_bytes(const btk_fb* fb, int S, int N, int per_stream, long tcount);
-int btk_big_analysis_bf_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                            int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
-int btk_big_analysis_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                                int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
-int btk_fast_synthesis_try(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
-                           long b0, long bcount, hipStream_t st);
+// fb_fused512.hip, FB_FUSED512: the production form of the fused kernel (M = 512, m = 4, r = 1), edge tiles first
+int btk_fused512(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                 int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
+// fb_fast.hip, FB_ANA_FAST / FB_FAST256 / FB_SYN_FAST: register-FFT kernels for M in {256,512,1024,2048}, m = 4 (fused: M = 256)
+int btk_fast_analysis(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, void* X,
+                      long T_stride, long t0, long tcount, hipStream_t st);
+int btk_fast_analysis_bf(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                         int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);
+int btk_fast_synthesis(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
+                       long b0, long bcount, hipStream_t st);
+// fb_fused_big.hip, FB_BIG: fused analysis -> fixed-weight beamformer for M = 1024 / 2048 (m = 4, r = 1)
+int btk_big_analysis_bf(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                        int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st);

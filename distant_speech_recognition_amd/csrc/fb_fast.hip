@@ -13,10 +13,38 @@
 #include "fft_lds.h"
 #include "fft_packed.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
 constexpr int F_NT = 256, F_MT = 4;
+
+// the launchers below are called for the routes fb_route.h gives this file; anything else is an error
+int not_covered(const char* who, const btk_fb* fb)
+{
+  return btk_set_error(BTK_ERR_PARAMETER, "%s: not a geometry of these kernels (M=%d m=%d r=%d)", who, fb->M, fb->m, fb->r);
+}
+
+// f(std::integral_constant<int, log2 M>) / f(std::integral_constant<int, R>) for the M (with m = 4) and the R these kernels are built for
+template <class F> int for_log2m(const char* who, const btk_fb* fb, F f)
+{
+  switch (fb->m == F_MT ? fb->M : 0) {
+    case 256:  return f(std::integral_constant<int, 8>{});
+    case 512:  return f(std::integral_constant<int, 9>{});
+    case 1024: return f(std::integral_constant<int, 10>{});
+    case 2048: return f(std::integral_constant<int, 11>{});
+  }
+  return not_covered(who, fb);
+}
+template <class F> int for_r(const char* who, const btk_fb* fb, F f)
+{
+  switch (fb->R) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+  }
+  return not_covered(who, fb);
+}
 
 __device__ __forceinline__ void f_dft4p(float2& a0, float2& a1, float2& a2, float2& a3)
 {
@@ -369,7 +397,7 @@ int launch_fast_analysis(const btk_fb* fb, const PT* pcm, long nsamples, long pc
   constexpr int FB_BYTES = G::TT * G::FRS * 8;
   constexpr int REG_U = ((SPAN * 4 > FB_BYTES) ? SPAN * 4 : FB_BYTES + 15) & ~15;
   const size_t lds = REG_U + sizeof(float2) * G::NF;
-  if (lds > 160 * 1024) return 0;
+  if (lds > 160 * 1024) return not_covered("btk_fast_analysis", fb);
   const int nchan = S * N;
   const int ntiles = (int)((tcount + G::TT - 1) / G::TT);
   const int nruns = (ntiles + F_RUN - 1) / F_RUN;
@@ -382,26 +410,14 @@ int launch_fast_analysis(const btk_fb* fb, const PT* pcm, long nsamples, long pc
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(F_NT), lds, st, pcm, nsamples, pcm_stride, fb->d_proto, fb->d_tw,
                      fb->laN, gain, N, fb->kx1 - fb->kx0, X, T_stride, t0, tcount, ntiles, nruns, nchan, fb->kx0, fb->kx1);
   BTK_HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-template <int LOG2M, typename PT = float>
-int fast_analysis_r(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, float2* X,
-                    long T_stride, long t0, long tcount, hipStream_t st)
-{
-  switch (fb->R) {
-    case 1: return launch_fast_analysis<LOG2M, 1, PT>(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
-    case 2: return launch_fast_analysis<LOG2M, 2, PT>(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
-    case 4: return launch_fast_analysis<LOG2M, 4, PT>(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
-  }
-  return 0;
+  return BTK_OK;
 }
 
 
 // ------------------------------------------------------------------------------------------------ fused analysis -> apply
 // OverSampledDFTAnalysisBank x N -> SubbandDS/GSC/MVDR::next for static weights (beamformer.cc:1267-1311 over
-// modulated.cc:375-409) at M = 256, the reference's default geometry, m = 4 (M = 512 has its own kernel in
-// fb_analysis512.hip; the template also instantiates for M = 1024 / 2048 but spills there and is not dispatched).
+// modulated.cc:375-409) at M = 256, the reference's default geometry, m = 4 (M = 512 has its own kernels in
+// fb_fused512.hip and fb_analysis512.hip; the template also instantiates for M = 1024 / 2048 but spills there and is not dispatched).
 // One workgroup = one (stream, TT-frame tile); it walks over the N channels, transforms each exactly as
 // fast_analysis_kernel does and adds conj(w_n[k]) X_n[k][t] to the bins it owns: thread (f = tid % TT, kq = tid / TT)
 // keeps bins kq, kq + KQ, ... of frame f in registers.  The N x K snapshot block never reaches HBM.
@@ -600,7 +616,7 @@ int launch_fast_analysis_bf(const btk_fb* fb, const PT* pcm, long nsamples, long
   constexpr int FB_BYTES = G::TT * G::FRS * 8;
   constexpr int REG_U = ((SPAN * 4 > FB_BYTES) ? SPAN * 4 : FB_BYTES + 15) & ~15;
   const size_t lds = REG_U + sizeof(float2) * (G::NF + G::NF + 1);
-  if (lds > 160 * 1024) return 0;
+  if (lds > 160 * 1024) return not_covered("btk_fast_analysis_bf", fb);
   const int K = fb->K, Sw = per_stream ? S : 1;
   const long nw = (long)Sw * K * N;
   hipLaunchKernelGGL(f_transpose_weights_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, W, Wt, K, N, Sw);
@@ -614,19 +630,7 @@ int launch_fast_analysis_bf(const btk_fb* fb, const PT* pcm, long nsamples, long
   hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(F_NT), lds, st, pcm, nsamples, pcm_stride, fb->d_proto, fb->d_tw,
                      fb->laN, gain, N, K, Wt, per_stream ? (long)N * K : 0L, Y, T_stride, t0, tcount, ntiles, tiles_per_xcd, S);
   BTK_HIP_CHECK(hipGetLastError());
-  return 1;
-}
-
-template <int LOG2M, typename PT = float>
-int fast_analysis_bf_r(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, const float2* W,
-                       int per_stream, float2* Wt, float2* Y, long T_stride, long t0, long tcount, hipStream_t st)
-{
-  switch (fb->R) {
-    case 1: return launch_fast_analysis_bf<LOG2M, 1, PT>(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream, Wt, Y, T_stride, t0, tcount, st);
-    case 2: return launch_fast_analysis_bf<LOG2M, 2, PT>(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream, Wt, Y, T_stride, t0, tcount, st);
-    case 4: return launch_fast_analysis_bf<LOG2M, 4, PT>(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream, Wt, Y, T_stride, t0, tcount, st);
-  }
-  return 0;
+  return BTK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ synthesis
@@ -998,7 +1002,7 @@ int launch_fast_synthesis(const btk_fb* fb, const float2* Y, long nframes, long 
   constexpr int HALO = F_MT * R - 1;
   constexpr int NRING = G::TT + HALO + 1;
   size_t lds = sizeof(float2) * ((size_t)NRING * G::FRS + G::NF);
-  if (lds > 160 * 1024) return 0;
+  if (lds > 160 * 1024) return not_covered("btk_fast_synthesis", fb);
   auto kern = fast_synthesis_kernel<LOG2M, R>;
   // the register-history form (M >= 1024): 16-byte rows on both sides -- even frame index of every chunk start (b0 + pd even; runs are
   // multiples of TT), Y rows and output blocks 16-byte aligned
@@ -1016,88 +1020,57 @@ int launch_fast_synthesis(const btk_fb* fb, const float2* Y, long nframes, long 
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)S), dim3(F_NT), lds, st, Y, nframes, T_stride, fb->K, fb->d_proto, fb->d_tw,
                      fb->pd, (float)fb->gain_factor, out, out_stride, b0, bcount, (int)srun);
   BTK_HIP_CHECK(hipGetLastError());
-  return 1;
+  return BTK_OK;
 }
 
-template <int LOG2M>
-int fast_synthesis_r(const btk_fb* fb, const float2* Y, long nframes, long T_stride, int S, float* out, long out_stride,
-                     long b0, long bcount, hipStream_t st)
+template <typename PT>
+int fast_analysis_m(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, float2* X,
+                    long T_stride, long t0, long tcount, hipStream_t st)
 {
-  switch (fb->R) {
-    case 1: return launch_fast_synthesis<LOG2M, 1>(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 2: return launch_fast_synthesis<LOG2M, 2>(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 4: return launch_fast_synthesis<LOG2M, 4>(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-  }
-  return 0;
+  return for_log2m("btk_fast_analysis", fb, [&](auto L) { return for_r("btk_fast_analysis", fb, [&](auto R) {
+    return launch_fast_analysis<decltype(L)::value, decltype(R)::value, PT>(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st); }); });
+}
+
+// fused analysis + beamformer at M = 256
+template <typename PT>
+int fast_analysis_bf_m(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, const float2* W,
+                       int per_stream, float2* Wt, float2* Y, long T_stride, long t0, long tcount, hipStream_t st)
+{
+  return for_r("btk_fast_analysis_bf", fb, [&](auto R) {
+    return launch_fast_analysis_bf<8, decltype(R)::value, PT>(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream, Wt, Y, T_stride, t0, tcount, st); });
 }
 
 }  // namespace
 
-// returns 1 handled / 0 geometry not covered / <0 error
-int btk_fast_analysis_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
-                          long T_stride, long t0, long tcount, hipStream_t st)
+// The routes of fb_route.h that this file implements; i16: pcm holds 16-bit samples.
+// FB_ANA_FAST (M = 512 has its own kernel in fb_analysis512.hip and comes here under BTK_DISABLE_ANALYSIS512)
+int btk_fast_analysis(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, void* X,
+                      long T_stride, long t0, long tcount, hipStream_t st)
 {
-  if (fb->m != F_MT) return 0;
   float2* Xp = static_cast<float2*>(X);
-  switch (fb->M) {
-    case 256:  return fast_analysis_r<8>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 512:  return fast_analysis_r<9>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 1024: return fast_analysis_r<10>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 2048: return fast_analysis_r<11>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-  }
-  return 0;
+  if (!i16) return fast_analysis_m(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
+  return fast_analysis_m(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
 }
 
-// the same from 16-bit PCM (btk_fb_analysis_i16; M = 512 has its own kernel in fb_analysis512.hip)
-int btk_fast_analysis_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
-                              long T_stride, long t0, long tcount, hipStream_t st)
+// FB_FAST256: fused analysis + fixed-weight beamformer for M = 256 (the reference's default geometry), m = 4; scratch: Sw K N complex64.
+// (M = 1024 / 2048: 32 accumulators + 32-point passes + two pair indices per thread spill ~1 KB of scratch per thread in this form;
+//  those geometries have fb_fused_big.hip)
+int btk_fast_analysis_bf(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                         int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
 {
-  if (fb->m != F_MT) return 0;
-  float2* Xp = static_cast<float2*>(X);
-  switch (fb->M) {
-    case 256:  return fast_analysis_r<8, short>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 512:  return fast_analysis_r<9, short>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 1024: return fast_analysis_r<10, short>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-    case 2048: return fast_analysis_r<11, short>(fb, pcm, nsamples, pcm_stride, S, N, Xp, T_stride, t0, tcount, st);
-  }
-  return 0;
-}
-
-// fused analysis + fixed-weight beamformer for M = 256 from 16-bit PCM (btk_fb_analysis_bf_i16)
-int btk_fast_analysis_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                                 int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
-{
-  if (fb->m != F_MT || fb->M != 256) return 0;
-  return fast_analysis_bf_r<8, short>(fb, pcm, nsamples, pcm_stride, S, N, static_cast<const float2*>(W), per_stream, static_cast<float2*>(Wt_scratch),
-                                      static_cast<float2*>(Y), T_stride, t0, tcount, st);
-}
-
-// fused analysis + fixed-weight beamformer for M = 256 (the reference's default geometry), m = 4; scratch: Sw K N complex64
-int btk_fast_analysis_bf_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                             int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
-{
-  if (fb->m != F_MT) return 0;
+  if (fb->m != F_MT || fb->M != 256) return not_covered("btk_fast_analysis_bf", fb);
   const float2* Wp = static_cast<const float2*>(W);
   float2* Wt = static_cast<float2*>(Wt_scratch);
   float2* Yp = static_cast<float2*>(Y);
-  switch (fb->M) {
-    // M = 1024 / 2048: 32 accumulators + 32-point passes + two pair indices per thread spill ~1 KB of scratch per thread
-    // in this form; those geometries stay with the staged pair until the accumulators move to the Z domain
-    case 256:  return fast_analysis_bf_r<8>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, Wt, Yp, T_stride, t0, tcount, st);
-  }
-  return 0;
+  return i16 ? fast_analysis_bf_m(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt, Yp, T_stride, t0, tcount, st)
+             : fast_analysis_bf_m(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt, Yp, T_stride, t0, tcount, st);
 }
 
-int btk_fast_synthesis_try(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
-                           long b0, long bcount, hipStream_t st)
+// FB_SYN_FAST
+int btk_fast_synthesis(const btk_fb* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
+                       long b0, long bcount, hipStream_t st)
 {
-  if (fb->m != F_MT) return 0;
   const float2* Yp = static_cast<const float2*>(Y);
-  switch (fb->M) {
-    case 256:  return fast_synthesis_r<8>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 512:  return fast_synthesis_r<9>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 1024: return fast_synthesis_r<10>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 2048: return fast_synthesis_r<11>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-  }
-  return 0;
+  return for_log2m("btk_fast_synthesis", fb, [&](auto L) { return for_r("btk_fast_synthesis", fb, [&](auto R) {
+    return launch_fast_synthesis<decltype(L)::value, decltype(R)::value>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st); }); });
 }

@@ -29,6 +29,7 @@ constexpr int F_SPAN = (F_TT - 1) * F_D + F_MT * F_M;                // samples 
 constexpr int F_FRZ = 272;                                          // float2 per FFT frame buffer (16 (mod 32): see fb_analysis512.hip)
 constexpr int F_FB_BYTES = F_TT * F_FRZ * 8;
 constexpr int F_WSTR = 320;                                         // float4 per channel in the weight-pair table
+static_assert(F_WSTR == FB_WSTR512, "btk_fb_analysis_bf_scratch_bytes sizes the weight-pair table by fb_route.h");
 constexpr int F_WQ_OFF = F_FB_BYTES;
 constexpr int F_LDS = F_FB_BYTES + 2 * F_WSTR * 16;                 // frames (the staged loop's span aliases them) + two weight-pair buffers
 constexpr int F_NV4 = (F_SPAN / 4 + F_NT - 1) / F_NT;
@@ -449,18 +450,15 @@ int launch_fused512(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_str
 
 }  // namespace
 
-// Fused analysis + fixed-weight beamformer, production form (M = 512, m = 4, r = 1, whole bin range, no diagnostic variant selected);
-// i16: pcm holds 16-bit samples.  Returns 1 if handled, 0 if the launch is not covered (the caller goes on to btk_analysis512_bf_try /
-// btk_analysis512_bf_i16_try), <0 on error
-int btk_fused512_try(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
-                     int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
+// Fused analysis + fixed-weight beamformer, production form: the FB_FUSED512 route of fb_route.h (M = 512, m = 4, r = 1, whole bin
+// range, no diagnostic variant selected); i16: pcm holds 16-bit samples
+int btk_fused512(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                 int per_stream, void* Wt_scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
 {
-  if (fb->M != F_M || fb->m != F_MT || fb->R != 2) return 0;
-  if (fb->kx0 != 0 || fb->kx1 != fb->K) return 0;
-  if (btk_switches().fused_var >= 0 || !btk_switches().fused512_new) return 0;
+  if (fb->M != F_M || fb->m != F_MT || fb->R != 2 || fb->kx0 != 0 || fb->kx1 != fb->K)
+    return btk_set_error(BTK_ERR_PARAMETER, "btk_fused512: not the geometry of this kernel (M=%d m=%d r=%d)", fb->M, fb->m, fb->r);
   const float2* Wp = static_cast<const float2*>(W);
   float2* Yp = static_cast<float2*>(Y);
-  const int rc = i16 ? launch_fused512<short>(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt_scratch, Yp, T_stride, t0, tcount, st)
-                     : launch_fused512<float>(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt_scratch, Yp, T_stride, t0, tcount, st);
-  return rc == BTK_OK ? 1 : rc;
+  return i16 ? launch_fused512<short>(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt_scratch, Yp, T_stride, t0, tcount, st)
+             : launch_fused512<float>(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, Wp, per_stream, Wt_scratch, Yp, T_stride, t0, tcount, st);
 }

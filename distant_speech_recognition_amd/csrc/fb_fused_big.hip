@@ -26,12 +26,14 @@
 // One stream of a large array has few tiles (512 frames = 64): the channels are then split over CG workgroups per tile whose
 // partial sums go to a scratch block and are added by a second, tiny kernel in a fixed order (bit-reproducible, no atomics).
 #include "btk_internal.h"
+#include "fb_route.h"
 #include "fft_packed.h"
 #include <type_traits>
 
 namespace {
 
 constexpr int B_MT = 4, B_TT = 8;
+static_assert(B_TT == FB_BIG_TT, "big_cg (fb_route.h) counts the tiles of this kernel");
 typedef unsigned u2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
@@ -401,16 +403,7 @@ void analysis_bfz_big_kernel(const PT* __restrict__ pcm, long nsamples, long pcm
   }
 }
 
-// channel groups per tile: enough workgroups for the chip (about two per CU of work items), never fewer than 8 channels per group
-// (C5 block, 64 tiles: 8 groups 0.279 ms, 4 groups -- one round of 256 workgroups -- 0.286, 16 groups 0.298)
-inline int big_cg(int S, int N, long tcount)
-{
-  const long tiles = (tcount + B_TT - 1) / B_TT * (long)S;
-  int cg = 1;
-  while (cg < 16 && tiles * cg < 384 && N / (2 * cg) >= 8) cg *= 2;
-  return cg;
-}
-
+// (channel groups per tile: big_cg of fb_route.h, which also sizes the partial blocks in `scratch`)
 template <int LOG2M, typename PT = float>
 int launch_big(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, const float2* W, int per_stream,
                void* scratch, float2* Y, long T_stride, long t0, long tcount, hipStream_t st)
@@ -453,38 +446,24 @@ int launch_big(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, 
   return BTK_OK;
 }
 
+// the FB_BIG route of fb_route.h; scratch: fb_fused_scratch_bytes (weight pairs + the partial blocks of a channel-split launch)
+template <typename PT>
+int big_analysis_bf(const btk_fb* fb, const PT* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
+                    int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
+{
+  const float2* Wp = static_cast<const float2*>(W);
+  float2* Yp = static_cast<float2*>(Y);
+  if (fb->M == 1024) return launch_big<10, PT>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
+  return launch_big<11, PT>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
+}
+
 }  // namespace
 
-// bytes of scratch btk_fb_analysis_bf needs for these geometries (weight pairs + the partial blocks of a channel-split launch); 0 = not covered
-long btk_big_analysis_bf_scratch_bytes(const btk_fb* fb, int S, int N, int per_stream, long tcount)
+int btk_big_analysis_bf(const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N, const void* W,
+                        int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
 {
-  if (fb->m != B_MT || fb->R != 2 || (fb->M != 1024 && fb->M != 2048) || fb->kx0 != 0 || fb->kx1 != fb->K) return 0;
-  const long wstr = fb->M / 2 + 16;
-  const int CG = big_cg(S, N, tcount);
-  return (long)sizeof(float4) * (per_stream ? S : 1) * N * wstr + (CG > 1 ? (long)sizeof(float2) * CG * S * fb->K * tcount : 0) + 16;
-}
-
-int btk_big_analysis_bf_try(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                            int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
-{
-  if (btk_big_analysis_bf_scratch_bytes(fb, S, N, per_stream, tcount) == 0) return 0;
-  const float2* Wp = static_cast<const float2*>(W);
-  float2* Yp = static_cast<float2*>(Y);
-  int rc;
-  if (fb->M == 1024) rc = launch_big<10>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
-  else rc = launch_big<11>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
-  return rc == BTK_OK ? 1 : rc;
-}
-
-// the same from 16-bit PCM (btk_fb_analysis_bf_i16)
-int btk_big_analysis_bf_i16_try(const btk_fb* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N, const void* W,
-                                int per_stream, void* scratch, void* Y, long T_stride, long t0, long tcount, hipStream_t st)
-{
-  if (btk_big_analysis_bf_scratch_bytes(fb, S, N, per_stream, tcount) == 0) return 0;
-  const float2* Wp = static_cast<const float2*>(W);
-  float2* Yp = static_cast<float2*>(Y);
-  int rc;
-  if (fb->M == 1024) rc = launch_big<10, short>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
-  else rc = launch_big<11, short>(fb, pcm, nsamples, pcm_stride, S, N, Wp, per_stream, scratch, Yp, T_stride, t0, tcount, st);
-  return rc == BTK_OK ? 1 : rc;
+  if (fb->m != B_MT || fb->R != 2 || (fb->M != 1024 && fb->M != 2048) || fb->kx0 != 0 || fb->kx1 != fb->K)
+    return btk_set_error(BTK_ERR_PARAMETER, "btk_big_analysis_bf: not a geometry of this kernel (M=%d m=%d r=%d)", fb->M, fb->m, fb->r);
+  if (!i16) return big_analysis_bf(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, W, per_stream, scratch, Y, T_stride, t0, tcount, st);
+  return big_analysis_bf(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, W, per_stream, scratch, Y, T_stride, t0, tcount, st);
 }

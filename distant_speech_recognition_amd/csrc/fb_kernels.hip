@@ -21,6 +21,7 @@
 #include "btk_internal.h"
 #include "fft_lds.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -322,6 +323,94 @@ int launch_synthesis(const btk_fb* fb, const float2* Y, long nframes, long T_str
   return rc > 0 ? BTK_OK : rc;
 }
 
+// one launch per power of two: f(std::integral_constant<int, log2 M>)
+template <class F> int for_log2m(int M, F f)
+{
+  switch (M) {
+    case 64:   return f(std::integral_constant<int, 6>{});
+    case 128:  return f(std::integral_constant<int, 7>{});
+    case 256:  return f(std::integral_constant<int, 8>{});
+    case 512:  return f(std::integral_constant<int, 9>{});
+    case 1024: return f(std::integral_constant<int, 10>{});
+    case 2048: return f(std::integral_constant<int, 11>{});
+  }
+  return btk_set_error(BTK_ERR_PARAMETER, "unsupported M=%d", M);
+}
+
+// the generic kernel: bins to X, or (P != nullptr) the polyphase sums to P
+int generic_analysis(const btk_fb* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, float2* X, float* P,
+                     long T_stride, long t0, long tcount, hipStream_t st)
+{
+  return for_log2m(fb->M, [&](auto L) { return launch_analysis<decltype(L)::value>(fb, pcm, nsamples, pcm_stride, S, N, X, P, T_stride, t0, tcount, st); });
+}
+
+// Which kernel covers a plan is decided by fb_route.h alone: the queries, the scratch size and the dispatch below all ask it, with
+// the A/B switches of profiles/ (btk_internal.h).
+fb_geom geom_of(const btk_fb* fb) { return fb_geom{fb->M, fb->m, fb->R, fb->K, fb->kx0 == 0 && fb->kx1 == fb->K, fb->synthesis != 0}; }
+
+// fb_analysis512.hip keeps the 1 launched / 0 not its geometry / < 0 error protocol; the route has chosen it, so 0 is an error too
+int launched512(int rc) { return rc > 0 ? BTK_OK : rc < 0 ? rc : btk_set_error(BTK_ERR_PARAMETER, "fb_analysis512: geometry not covered"); }
+
+// btk_fb_analysis / btk_fb_analysis_i16 (`who`: the entry point that was called; i16: pcm holds 16-bit samples)
+int analysis_entry(const char* who, const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride,
+                   int S, int N, void* X, long T_stride, long t0, long tcount, void* stream)
+{
+  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "%s: not an analysis plan", who);
+  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
+    return btk_set_error(BTK_ERR_DIMENSION, "%s: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", who, S, N, tcount, T_stride);
+  if (tcount == 0) return BTK_OK;
+  if (i16 && (!pcm || !X)) return btk_set_error(BTK_ERR_PARAMETER, "%s: null argument", who);   // (float: an empty recording may come as a null pointer)
+  hipStream_t st = as_stream(stream);
+  const fb_analysis_route_t rt = fb_analysis_route(geom_of(fb), btk_switches());
+  if (i16 && rt == FB_ANA_GENERIC)
+    return btk_set_error(BTK_ERR_PARAMETER, "%s: no int16 kernel for M=%d m=%d r=%d (btk_pcm_i16_to_f32 + btk_fb_analysis)", who, fb->M, fb->m, fb->r);
+  switch (rt) {
+    case FB_ANA_A512:
+      return launched512(i16 ? btk_analysis512_i16_try(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st)
+                             : btk_analysis512_try(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st));
+    case FB_ANA_FAST: return btk_fast_analysis(fb, pcm, i16, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
+    case FB_ANA_GENERIC: break;
+  }
+  return generic_analysis(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, static_cast<float2*>(X), nullptr, T_stride, t0, tcount, st);
+}
+
+// btk_fb_analysis_bf / btk_fb_analysis_bf_i16: fused OverSampledDFTAnalysisBank xN -> SubbandDS/GSC/MVDR::next for static weights.
+// FB_STAGED (float samples only) is the staged pair, btk_fb_analysis into `scratch` + btk_bf_apply.
+int analysis_bf_entry(const char* who, const btk_fb* fb, const void* pcm, int i16, long nsamples, long pcm_stride, int S, int N,
+                      const void* W, int per_stream_weights, void* Y, long T_stride, long t0, long tcount,
+                      void* scratch, long scratch_bytes, void* stream)
+{
+  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "%s: not an analysis plan", who);
+  if (!pcm || !W || !Y || !scratch) return btk_set_error(BTK_ERR_PARAMETER, "%s: null argument", who);
+  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
+    return btk_set_error(BTK_ERR_DIMENSION, "%s: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", who, S, N, tcount, T_stride);
+  if (tcount == 0) return BTK_OK;
+  if (reinterpret_cast<uintptr_t>(scratch) & 15) return btk_set_error(BTK_ERR_PARAMETER, "%s: scratch must be 16-byte aligned", who);
+  if (i16 && (reinterpret_cast<uintptr_t>(pcm) & 3)) return btk_set_error(BTK_ERR_PARAMETER, "%s: pcm must be 4-byte aligned", who);
+  const fb_geom g = geom_of(fb);
+  const fb_fused_route_t rt = fb_fused_route(g, btk_switches(), i16);
+  if (i16 && rt == FB_STAGED)
+    return btk_set_error(BTK_ERR_PARAMETER, "%s: no int16 kernel for M=%d m=%d r=%d (btk_pcm_i16_to_f32 + btk_fb_analysis_bf)", who, fb->M, fb->m, fb->r);
+  // the fused kernels stage their weights in `scratch` (fb_route.h has the layouts), the staged pair its snapshots
+  const long need = fb_fused_scratch_bytes(rt, g, S, N, per_stream_weights, tcount);
+  if (scratch_bytes < need) return btk_set_error(BTK_ERR_PARAMETER, "%s: scratch too small (%ld < %ld)", who, scratch_bytes, need);
+  hipStream_t st = as_stream(stream);
+  switch (rt) {
+    case FB_FUSED512: return btk_fused512(fb, pcm, i16, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+    case FB_BFZ512:
+      return launched512(i16 ? btk_analysis512_bf_i16_try(fb, static_cast<const short*>(pcm), nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st)
+                             : btk_analysis512_bf_try(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st));
+    case FB_BIG: return btk_big_analysis_bf(fb, pcm, i16, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+    case FB_FAST256: return btk_fast_analysis_bf(fb, pcm, i16, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
+    case FB_STAGED: break;
+  }
+  // the snapshots in `scratch` have T_stride == tcount; Y keeps the caller's stride only when they agree
+  if (T_stride != tcount) return btk_set_error(BTK_ERR_PARAMETER, "%s: staged fall-back needs T_stride == tcount", who);
+  const int rc = btk_fb_analysis(fb, static_cast<const float*>(pcm), nsamples, pcm_stride, S, N, scratch, tcount, t0, tcount, stream);
+  if (rc) return rc;
+  return btk_bf_apply(W, per_stream_weights, scratch, Y, S, fb->K, N, tcount, tcount, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -329,55 +418,19 @@ extern "C" {
 int btk_fb_analysis(const btk_fb_t* fb, const float* pcm, long nsamples, long pcm_stride,
                     int S, int N, void* X, long T_stride, long t0, long tcount, void* stream)
 {
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis: not an analysis plan");
-  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_analysis: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", S, N, tcount, T_stride);
-  if (tcount == 0) return BTK_OK;
-  hipStream_t st = as_stream(stream);
-  float2* Xp = static_cast<float2*>(X);
-  const bool no512 = btk_switches().disable_analysis512;                         // A/B switches of profiles/ (btk_internal.h)
-  if (!no512) {
-    const int rc = btk_analysis512_try(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
-    if (rc != 0) return rc > 0 ? BTK_OK : rc;
-  }
-  const bool nofast = btk_switches().disable_fast;
-  if (!nofast) {
-    const int rc = btk_fast_analysis_try(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, st);
-    if (rc != 0) return rc > 0 ? BTK_OK : rc;
-  }
-  switch (fb->M) {
-    case 64:   return launch_analysis<6>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-    case 128:  return launch_analysis<7>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-    case 256:  return launch_analysis<8>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-    case 512:  return launch_analysis<9>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-    case 1024: return launch_analysis<10>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-    case 2048: return launch_analysis<11>(fb, pcm, nsamples, pcm_stride, S, N, Xp, nullptr, T_stride, t0, tcount, st);
-  }
-  return btk_set_error(BTK_ERR_PARAMETER, "unsupported M=%d", fb->M);
-}
-
-int btk_fb_analysis_i16_direct(const btk_fb_t* fb)
-{
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16_direct: not an analysis plan");
-  if (fb->m != 4 || !(fb->R == 1 || fb->R == 2 || fb->R == 4)) return 0;
-  if (fb->M == 512 && !btk_switches().disable_analysis512) return 1;
-  return !btk_switches().disable_fast && (fb->M == 256 || fb->M == 512 || fb->M == 1024 || fb->M == 2048);
+  return analysis_entry("btk_fb_analysis", fb, pcm, 0, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, stream);
 }
 
 int btk_fb_analysis_i16(const btk_fb_t* fb, const short* pcm, long nsamples, long pcm_stride,
                         int S, int N, void* X, long T_stride, long t0, long tcount, void* stream)
 {
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16: not an analysis plan");
-  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_analysis_i16: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", S, N, tcount, T_stride);
-  if (tcount == 0) return BTK_OK;
-  if (!pcm || !X) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16: null argument");
-  if (btk_fb_analysis_i16_direct(fb) != 1)
-    return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16: no int16 kernel for M=%d m=%d r=%d (btk_pcm_i16_to_f32 + btk_fb_analysis)", fb->M, fb->m, fb->r);
-  int rc = btk_switches().disable_analysis512 ? 0 : btk_analysis512_i16_try(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, as_stream(stream));
-  if (rc == 0) rc = btk_fast_analysis_i16_try(fb, pcm, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, as_stream(stream));
-  if (rc == 0) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16: geometry not covered");
-  return rc > 0 ? BTK_OK : rc;
+  return analysis_entry("btk_fb_analysis_i16", fb, pcm, 1, nsamples, pcm_stride, S, N, X, T_stride, t0, tcount, stream);
+}
+
+int btk_fb_analysis_i16_direct(const btk_fb_t* fb)
+{
+  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_i16_direct: not an analysis plan");
+  return fb_analysis_route(geom_of(fb), btk_switches()) != FB_ANA_GENERIC;
 }
 
 int btk_fb_analysis_bins(const btk_fb_t* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
@@ -397,16 +450,7 @@ int btk_fb_analysis_polyphase(const btk_fb_t* fb, const float* pcm, long nsample
   if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_polyphase: not an analysis plan");
   if (S <= 0 || N <= 0 || tcount < 0) return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_analysis_polyphase: bad sizes");
   if (tcount == 0) return BTK_OK;
-  hipStream_t st = as_stream(stream);
-  switch (fb->M) {
-    case 64:   return launch_analysis<6>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-    case 128:  return launch_analysis<7>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-    case 256:  return launch_analysis<8>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-    case 512:  return launch_analysis<9>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-    case 1024: return launch_analysis<10>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-    case 2048: return launch_analysis<11>(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, st);
-  }
-  return btk_set_error(BTK_ERR_PARAMETER, "unsupported M=%d", fb->M);
+  return generic_analysis(fb, pcm, nsamples, pcm_stride, S, N, nullptr, P, tcount, t0, tcount, as_stream(stream));
 }
 
 int btk_fb_synthesis(const btk_fb_t* fb, const void* Y, long nframes, long T_stride, int S,
@@ -417,138 +461,52 @@ int btk_fb_synthesis(const btk_fb_t* fb, const void* Y, long nframes, long T_str
     return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_synthesis: bad sizes S=%d bcount=%ld nframes=%ld T_stride=%ld", S, bcount, nframes, T_stride);
   if (bcount == 0) return BTK_OK;
   hipStream_t st = as_stream(stream);
-  const float2* Yp = static_cast<const float2*>(Y);
-  const bool no512 = btk_switches().disable_synthesis512;
-  if (!no512) {
-    const int rc = btk_synthesis512_try(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    if (rc != 0) return rc > 0 ? BTK_OK : rc;
+  switch (fb_synthesis_route(geom_of(fb), btk_switches())) {
+    case FB_SYN_S512: return launched512(btk_synthesis512_try(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st));
+    case FB_SYN_FAST: return btk_fast_synthesis(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
+    case FB_SYN_GENERIC: break;
   }
-  const bool nofast = btk_switches().disable_fast;
-  if (!nofast) {
-    const int rc = btk_fast_synthesis_try(fb, Y, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    if (rc != 0) return rc > 0 ? BTK_OK : rc;
-  }
-  switch (fb->M) {
-    case 64:   return launch_synthesis<6>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 128:  return launch_synthesis<7>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 256:  return launch_synthesis<8>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 512:  return launch_synthesis<9>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 1024: return launch_synthesis<10>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-    case 2048: return launch_synthesis<11>(fb, Yp, nframes, T_stride, S, out, out_stride, b0, bcount, st);
-  }
-  return btk_set_error(BTK_ERR_PARAMETER, "unsupported M=%d", fb->M);
+  return for_log2m(fb->M, [&](auto L) { return launch_synthesis<decltype(L)::value>(fb, static_cast<const float2*>(Y), nframes, T_stride, S, out, out_stride, b0, bcount, st); });
 }
 
 int btk_fb_synthesis_aligned_form(const btk_fb_t* fb)
 {
   if (!fb || !fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_synthesis_aligned_form: not a synthesis plan");
-  if (btk_switches().syn_narrow || fb->m != 4 || fb->R > 2) return 0;
-  if (fb->M == 512) return btk_switches().disable_synthesis512 ? 0 : 1;      // synthesis512w_kernel (fb_analysis512.hip)
-  return (fb->M == 1024 || fb->M == 2048) && !btk_switches().disable_fast;   // fast_synthesis_w_kernel (fb_fast.hip)
+  return fb_synthesis_aligned_form(geom_of(fb), btk_switches());
 }
 
-// Fused OverSampledDFTAnalysisBank xN -> SubbandDS/GSC/MVDR::next for static weights.  Falls back to the staged
-// pair (btk_fb_analysis into `scratch` + btk_bf_apply) for geometries the fused kernel does not cover.
 int btk_fb_analysis_bf(const btk_fb_t* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N,
                        const void* W, int per_stream_weights, void* Y, long T_stride, long t0, long tcount,
                        void* scratch, long scratch_bytes, void* stream)
 {
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: not an analysis plan");
-  if (!pcm || !W || !Y || !scratch) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: null argument");
-  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_analysis_bf: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", S, N, tcount, T_stride);
-  if (tcount == 0) return BTK_OK;
-  if (reinterpret_cast<uintptr_t>(scratch) & 15) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: scratch must be 16-byte aligned");
-  // fused geometries stage their weights in `scratch`: pairs [Sw][N][320] float4 at M = 512 (fb_analysis512.hip), the
-  // transposed matrix [Sw][N][K] complex64 at M = 256 (fb_fast.hip); the staged fall-back checks its own size below
-  const bool fuse512 = fb->M == 512 && fb->m == 4;
-  const bool fusefast = fb->m == 4 && fb->M == 256 && (fb->R == 1 || fb->R == 2 || fb->R == 4);
-  const long Sw = per_stream_weights ? S : 1;
-  const long big_bytes = btk_big_analysis_bf_scratch_bytes(fb, S, N, per_stream_weights, tcount);      // M = 1024 / 2048 (fb_fused_big.hip)
-  const long wt_bytes = fuse512 ? (long)sizeof(float4) * Sw * 320 * N : fusefast ? (long)sizeof(float2) * Sw * fb->K * N : big_bytes;
-  hipStream_t st = as_stream(stream);
-  const bool nofuse = btk_switches().disable_fused;
-  if (!nofuse) {
-    if ((fuse512 || fusefast || big_bytes) && scratch_bytes < wt_bytes)
-      return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: scratch too small (%ld < %ld)", scratch_bytes, wt_bytes);
-    int rc = btk_fused512_try(fb, pcm, 0, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-    if (rc == 0) rc = btk_analysis512_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-    if (rc != 0) return rc > 0 ? BTK_OK : rc;
-    if (big_bytes) {
-      rc = btk_big_analysis_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-      if (rc != 0) return rc > 0 ? BTK_OK : rc;
-    }
-    if (fusefast) {
-      rc = btk_fast_analysis_bf_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-      if (rc != 0) return rc > 0 ? BTK_OK : rc;
-    }
-  }
-  const long x_bytes = (long)sizeof(float2) * S * fb->K * N * tcount;
-  if (scratch_bytes < x_bytes)
-    return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: staged fall-back needs %ld bytes of scratch for the snapshots", x_bytes);
-  int rc = btk_fb_analysis(fb, pcm, nsamples, pcm_stride, S, N, scratch, tcount, t0, tcount, stream);
-  if (rc) return rc;
-  // staged layout has T_stride == tcount for X; Y keeps the caller's stride only when they agree
-  if (T_stride != tcount) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf: staged fall-back needs T_stride == tcount");
-  return btk_bf_apply(W, per_stream_weights, scratch, Y, S, fb->K, N, tcount, tcount, stream);
-}
-
-int btk_fb_analysis_bf_fused(const btk_fb_t* fb)
-{
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_fused: not an analysis plan");
-  if (btk_switches().disable_fused || fb->m != 4 || fb->kx0 != 0 || fb->kx1 != fb->K) return 0;
-  const bool rok = fb->R == 1 || fb->R == 2 || fb->R == 4;
-  if ((fb->M == 512 || fb->M == 256) && rok) return 1;                       // fb_analysis512.hip, fb_fast.hip
-  return (fb->M == 1024 || fb->M == 2048) && fb->R == 2;                      // fb_fused_big.hip
-}
-
-int btk_fb_analysis_bf_i16_fused(const btk_fb_t* fb)
-{
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16_fused: not an analysis plan");
-  if (btk_switches().disable_fused || fb->m != 4 || fb->kx0 != 0 || fb->kx1 != fb->K) return 0;
-  if (fb->M == 256 && btk_switches().disable_fast) return 0;
-  if (fb->M == 512 || fb->M == 256) return fb->R == 1 || fb->R == 2 || fb->R == 4;
-  return (fb->M == 1024 || fb->M == 2048) && fb->R == 2;
+  return analysis_bf_entry("btk_fb_analysis_bf", fb, pcm, 0, nsamples, pcm_stride, S, N, W, per_stream_weights, Y, T_stride, t0, tcount, scratch, scratch_bytes, stream);
 }
 
 int btk_fb_analysis_bf_i16(const btk_fb_t* fb, const short* pcm, long nsamples, long pcm_stride, int S, int N,
                            const void* W, int per_stream_weights, void* Y, long T_stride, long t0, long tcount,
                            void* scratch, long scratch_bytes, void* stream)
 {
-  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: not an analysis plan");
-  if (!pcm || !W || !Y || !scratch) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: null argument");
-  if (S <= 0 || N <= 0 || tcount < 0 || T_stride < tcount || pcm_stride < nsamples)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_fb_analysis_bf_i16: bad sizes S=%d N=%d tcount=%ld T_stride=%ld", S, N, tcount, T_stride);
-  if (tcount == 0) return BTK_OK;
-  if (reinterpret_cast<uintptr_t>(scratch) & 15) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: scratch must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(pcm) & 3) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: pcm must be 4-byte aligned");
-  if (btk_fb_analysis_bf_i16_fused(fb) != 1)
-    return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: no int16 kernel for M=%d m=%d r=%d (btk_pcm_i16_to_f32 + btk_fb_analysis_bf)", fb->M, fb->m, fb->r);
-  const long need = btk_fb_analysis_bf_scratch_bytes(fb, S, N, per_stream_weights, tcount);
-  if (scratch_bytes < need) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: scratch too small (%ld < %ld)", scratch_bytes, need);
-  hipStream_t st = as_stream(stream);
-  int rc = btk_fused512_try(fb, pcm, 1, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-  if (rc == 0) rc = btk_analysis512_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-  if (rc == 0) rc = btk_big_analysis_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-  if (rc == 0 && !btk_switches().disable_fast) rc = btk_fast_analysis_bf_i16_try(fb, pcm, nsamples, pcm_stride, S, N, W, per_stream_weights, scratch, Y, T_stride, t0, tcount, st);
-  if (rc == 0) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16: geometry not covered");
-  return rc > 0 ? BTK_OK : rc;
+  return analysis_bf_entry("btk_fb_analysis_bf_i16", fb, pcm, 1, nsamples, pcm_stride, S, N, W, per_stream_weights, Y, T_stride, t0, tcount, scratch, scratch_bytes, stream);
 }
 
+int btk_fb_analysis_bf_fused(const btk_fb_t* fb)
+{
+  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_fused: not an analysis plan");
+  return fb_fused_route(geom_of(fb), btk_switches(), 0) != FB_STAGED;
+}
+
+int btk_fb_analysis_bf_i16_fused(const btk_fb_t* fb)
+{
+  if (!fb || fb->synthesis) return btk_set_error(BTK_ERR_PARAMETER, "btk_fb_analysis_bf_i16_fused: not an analysis plan");
+  return fb_fused_route(geom_of(fb), btk_switches(), 1) != FB_STAGED;
+}
+
+// (no sample type here: the size of the float entry's route, which the int16 entry shares wherever it has a kernel)
 long btk_fb_analysis_bf_scratch_bytes(const btk_fb_t* fb, int S, int N, int per_stream_weights, long tcount)
 {
   if (!fb) return -1;
-  const bool rok = fb->R == 1 || fb->R == 2 || fb->R == 4;
-  const bool nofuse = btk_switches().disable_fused;
-  if (!nofuse && rok && fb->m == 4 && fb->M == 512)
-    return (long)sizeof(float4) * (per_stream_weights ? S : 1) * 320 * N;                // weight pairs [Sw][N][320], see fb_analysis512.hip
-  if (!nofuse && rok && fb->m == 4 && fb->M == 256)
-    return (long)sizeof(float2) * (per_stream_weights ? S : 1) * fb->K * N;              // transposed weights [Sw][N][K], see fb_fast.hip
-  if (!nofuse) {
-    const long big = btk_big_analysis_bf_scratch_bytes(fb, S, N, per_stream_weights, tcount);   // weight pairs + channel-group partial blocks
-    if (big) return big;
-  }
-  return (long)sizeof(float2) * S * fb->K * N * tcount;
+  const fb_geom g = geom_of(fb);
+  return fb_fused_scratch_bytes(fb_fused_route(g, btk_switches(), 0), g, S, N, per_stream_weights, tcount);
 }
 
 }  // extern "C"
