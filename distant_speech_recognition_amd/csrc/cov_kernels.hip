@@ -15,7 +15,9 @@
 //   cov_valu_kernel : same tiling on the vector ALU, used for parity cross-checks and N < 16.
 //
 // Weights: wt [S][K][T] float32 (TF mask, frames contiguous) or wf [S][T] (frame gate); both
-// optional.  R [S][K][N][N] complex64 row-major, accumulated in place (+=).
+// optional.  R [S][K][N][N] complex64 row-major, accumulated in place (+=).  A frame whose weight
+// is 0 contributes nothing in any kernel, even if its snapshot is NaN or Inf: the reference skips
+// it (pybeamformer.py:1080, :1137-1147).
 #include "btk_internal.h"
 
 namespace {
@@ -25,10 +27,22 @@ constexpr int CLD = CT + 1;            // padded row (float2 units)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// Stage rows [row0, row0+64) of A_k (zero beyond N) for frames [t0, t0+CT) scaled by nothing;
-// weight vector for the tile goes to wrow[CT].
+__device__ __forceinline__ float tile_weight(const float* __restrict__ wt, const float* __restrict__ wf, long t, long T)
+{
+  if (t >= T) return 0.f;
+  float w = 1.f;
+  if (wt) w *= wt[t];
+  if (wf) w *= wf[t];
+  return w;
+}
+
+// Stage rows [row0, row0+64) of A_k (zero beyond N) for frames [t0, t0+CT) scaled by nothing.
+// wl[CT] holds the tile's weights (LDS): a frame of weight 0 is staged as zero, whatever it holds
+// (NaN * 0 would be NaN): the select comes before any multiply.
+template <bool WEIGHTED>
 __device__ __forceinline__ void stage_tile(const float2* __restrict__ Xk, int N, long T_stride, long T,
-                                           int row0, long t0, float2* __restrict__ dst, int tid, int nthreads)
+                                           int row0, long t0, float2* __restrict__ dst, int tid, int nthreads,
+                                           const float* __restrict__ wl)
 {
   // 16 lanes x float4 (2 frames) = 32 frames = 256 B per row
   for (int idx = tid; idx < 64 * (CT / 2); idx += nthreads) {
@@ -41,18 +55,14 @@ __device__ __forceinline__ void stage_tile(const float2* __restrict__ Xk, int N,
       if (t < T) a = p[0];
       if (t + 1 < T) b = p[1];
     }
+    if (WEIGHTED) {
+      const float2 z = make_float2(0.f, 0.f);
+      a = wl[2 * c2] != 0.f ? a : z;
+      b = wl[2 * c2 + 1] != 0.f ? b : z;
+    }
     dst[r * CLD + 2 * c2] = a;
     dst[r * CLD + 2 * c2 + 1] = b;
   }
-}
-
-__device__ __forceinline__ float tile_weight(const float* __restrict__ wt, const float* __restrict__ wf, long t, long T)
-{
-  if (t >= T) return 0.f;
-  float w = 1.f;
-  if (wt) w *= wt[t];
-  if (wf) w *= wf[t];
-  return w;
 }
 
 // grid: (tiles_i * tiles_j, K, S); block 256 threads = 4 waves (2x2 quadrants of 32x32)
@@ -63,7 +73,7 @@ void cov_mfma_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2* Ai = reinterpret_cast<float2*>(smem);          // [64][CLD] rows of the i-tile
   float2* Aj = Ai + 64 * CLD;                            // [64][CLD] rows of the j-tile (weighted)
-  float* wrow = reinterpret_cast<float*>(Aj + 64 * CLD); // [CT]
+  float* wrow = reinterpret_cast<float*>(Aj + 64 * CLD); // [2][CT]: the weights of a tile are written while the tile before it is multiplied
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int k = blockIdx.y, s = blockIdx.z;
   const int ti = blockIdx.x / ntile, tj = blockIdx.x % ntile;
@@ -80,6 +90,7 @@ void cov_mfma_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
   constexpr int PER = 64 * (CT / 2) / 256;               // float4 pairs per thread and row tile (= 4)
   float4 pi_[PER], pj_[PER];
   float wnext = 0.f;
+  const bool weighted = wt || wf;                        // uniform
   auto prefetch = [&](long t0) {
 #pragma unroll
     for (int q = 0; q < PER; q++) {
@@ -104,7 +115,17 @@ void cov_mfma_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
     }
     if (tid < CT) wnext = tile_weight(wt, wf, t0 + tid, T);
   };
-  auto commit = [&]() {
+  auto commit = [&](const float* wl) {
+    // a frame of weight 0 is staged as zero, whatever it holds (NaN * 0 would be NaN): the select comes before any multiply.
+    // A thread stages the same two frames in every row it handles.
+    if (weighted) {
+      const bool on0 = wl[2 * (tid % (CT / 2))] != 0.f, on1 = wl[2 * (tid % (CT / 2)) + 1] != 0.f;
+#pragma unroll
+      for (int q = 0; q < PER; q++) {
+        if (!on0) { pi_[q].x = 0.f; pi_[q].y = 0.f; pj_[q].x = 0.f; pj_[q].y = 0.f; }
+        if (!on1) { pi_[q].z = 0.f; pi_[q].w = 0.f; pj_[q].z = 0.f; pj_[q].w = 0.f; }
+      }
+    }
 #pragma unroll
     for (int q = 0; q < PER; q++) {
       const int idx = tid + q * 256;
@@ -116,20 +137,22 @@ void cov_mfma_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
         Aj[r * CLD + 2 * c2 + 1] = make_float2(pj_[q].z, pj_[q].w);
       }
     }
-    if (tid < CT) wrow[tid] = wnext;
   };
 
   prefetch(0);
-  for (long t0 = 0; t0 < T; t0 += CT) {
+  if (tid < CT) wrow[tid] = wnext;
+  int par = 0;
+  for (long t0 = 0; t0 < T; t0 += CT, par ^= 1) {
+    const float* wl = wrow + par * CT;
     __syncthreads();
-    commit();
+    commit(wl);
     __syncthreads();
     if (t0 + CT < T) prefetch(t0 + CT);
 #pragma unroll 4
     for (int kk = 0; kk < CT; kk += 2) {
       const float2 a = Ai[(qi * 32 + li) * CLD + kk + lk];
       float2 b = Bj[(qj * 32 + li) * CLD + kk + lk];
-      const float w = wrow[kk + lk];
+      const float w = wl[kk + lk];
       b.x *= w; b.y *= w;
       // Rr += ar br + ai bi ; Ri += ai br - ar bi      (R_ij = a_i conj(b_j))
       rr = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, rr, 0, 0, 0);
@@ -137,6 +160,8 @@ void cov_mfma_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
       ri = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, ri, 0, 0, 0);
       ri = __builtin_amdgcn_mfma_f32_32x32x2f32(-a.x, b.y, ri, 0, 0, 0);
     }
+    // the next tile's weights go to the other half of wrow: nobody reads that half between the barrier above and the next one
+    if (t0 + CT < T && tid < CT) wrow[(par ^ 1) * CT + tid] = wnext;
   }
   // C/D layout of 32x32: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
   float2* Rk = R + ((long)s * K + k) * N * N;
@@ -160,7 +185,7 @@ void cov_valu_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2* Ai = reinterpret_cast<float2*>(smem);
   float2* Aj = Ai + 64 * CLD;
-  float* wrow = reinterpret_cast<float*>(Aj + 64 * CLD);
+  float* wrow = reinterpret_cast<float*>(Aj + 64 * CLD); // [2][CT], as in cov_mfma_kernel
   const int tid = threadIdx.x;
   const int k = blockIdx.y, s = blockIdx.z;
   const int ti = blockIdx.x / ntile, tj = blockIdx.x % ntile;
@@ -173,14 +198,24 @@ void cov_valu_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
   for (int p = 0; p < 4; p++)
 #pragma unroll
     for (int q = 0; q < 4; q++) acc[p][q] = make_float2(0.f, 0.f);
-  for (long t0 = 0; t0 < T; t0 += CT) {
+  if (tid < CT) wrow[tid] = tile_weight(wt, wf, tid, T);
+  int par = 0;
+  for (long t0 = 0; t0 < T; t0 += CT, par ^= 1) {
+    const float* wl = wrow + par * CT;
     __syncthreads();
-    stage_tile(Xk, N, T_stride, T, ti * 64, t0, Ai, tid, 256);
-    stage_tile(Xk, N, T_stride, T, tj * 64, t0, Aj, tid, 256);
-    if (tid < CT) wrow[tid] = tile_weight(wt, wf, t0 + tid, T);
+    if (wt || wf) {                                      // uniform
+      stage_tile<true>(Xk, N, T_stride, T, ti * 64, t0, Ai, tid, 256, wl);
+      stage_tile<true>(Xk, N, T_stride, T, tj * 64, t0, Aj, tid, 256, wl);
+    } else {
+      stage_tile<false>(Xk, N, T_stride, T, ti * 64, t0, Ai, tid, 256, wl);
+      stage_tile<false>(Xk, N, T_stride, T, tj * 64, t0, Aj, tid, 256, wl);
+    }
+    const bool more = t0 + CT < T && tid < CT;
+    float wnext = 0.f;
+    if (more) wnext = tile_weight(wt, wf, t0 + CT + tid, T);
     __syncthreads();
     for (int tt = 0; tt < CT; tt++) {
-      const float w = wrow[tt];
+      const float w = wl[tt];
       float2 xi[4], xj[4];
 #pragma unroll
       for (int p = 0; p < 4; p++) xi[p] = Ai[(a + 16 * p) * CLD + tt];
@@ -194,6 +229,7 @@ void cov_valu_kernel(const float2* __restrict__ X, const float* __restrict__ WT,
           acc[p][q].y = fmaf(xi[p].y, xj[q].x, fmaf(-xi[p].x, xj[q].y, acc[p][q].y));
         }
     }
+    if (more) wrow[(par ^ 1) * CT + tid] = wnext;        // read only after the next barrier
   }
   float2* Rk = R + ((long)s * K + k) * N * N;
 #pragma unroll
@@ -361,7 +397,7 @@ int btk_cov_accumulate(const void* X, const float* tf_weights, const float* fram
     return BTK_OK;
   }
   const int ntile = (N + 63) / 64;
-  const size_t lds = sizeof(float2) * 2 * 64 * CLD + sizeof(float) * CT;
+  const size_t lds = sizeof(float2) * 2 * 64 * CLD + sizeof(float) * 2 * CT;
   dim3 grid((unsigned)(ntile * ntile), (unsigned)K, (unsigned)S);
   if (use_mfma)
     hipLaunchKernelGGL(cov_mfma_kernel, grid, dim3(256), lds, as_stream(stream), static_cast<const float2*>(X),

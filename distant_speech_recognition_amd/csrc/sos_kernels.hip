@@ -11,8 +11,10 @@
 // design steps -- the per-frame work stays in btk_bf_apply.
 //
 // GEV: Rn = L L^H, C = L^-1 Rt L^-H (Hermitian PSD), principal eigenvector of C by repeated squaring
-// C <- C^2 / tr(C^2) (32 squarings = power 2^32: separates eigenvalue ratios up to 1 - 1e-9), v = the column of
+// C <- C^2 / tr(C^2) (32 squarings = power 2^32: a second eigenvalue at ratio 1 - g is left at (1 - g)^(2^32), which is
+// 2e-19 for g = 1e-8 and still 1.4e-2 for g = 1e-9, so ratios up to about 1 - 1e-8 are separated), v = the column of
 // the resulting rank-one matrix with the largest diagonal, w = L^-H v / |v|  (w^H Rn w = 1 like scipy's eigh).
+// A target covariance without a positive trace is replaced by I / N: finite weights, not counted as failed.
 #include "btk_internal.h"
 
 namespace {
@@ -199,17 +201,19 @@ void gev_vectors_kernel(const float2* __restrict__ Rt, const float2* __restrict_
   forward_solve_cols(L, C2, N, tid);
   for (int e = tid; e < N * N; e += SOS_NT) { const int i = e / N, j = e % N; C[(long)j * N + i] = zconj(C2[e]); }
   __syncthreads();
-  // symmetrise (rounding) and scale to unit trace
+  // symmetrise (rounding) and scale to unit trace; returns the trace it found
   auto normalise = [&](zd* A) {
     double p = 0.0;
     for (int i = tid; i < N; i += SOS_NT) p += A[(long)i * N + i].x;
     red[tid] = p;
     __syncthreads();
     for (int o = SOS_NT / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-    const double inv = red[0] > 0.0 ? 1.0 / red[0] : 0.0;
+    const double tr = red[0];
+    const double inv = tr > 0.0 ? 1.0 / tr : 0.0;
     __syncthreads();
     for (int e = tid; e < N * N; e += SOS_NT) A[e] = zscale(A[e], inv);
     __syncthreads();
+    return tr;
   };
   for (int e = tid; e < N * N; e += SOS_NT) {
     const int i = e / N, j = e % N;
@@ -220,7 +224,12 @@ void gev_vectors_kernel(const float2* __restrict__ Rt, const float2* __restrict_
     } else if (i == j) C[e].y = 0.0;
   }
   __syncthreads();
-  normalise(C);
+  if (!(normalise(C) > 0.0)) {                                      // uniform
+    // no positive trace (an all-zero target covariance): every vector is principal.  I / N keeps the squarings, the column
+    // pick and the norm finite and ends in w = L^-H e_0 with w^H Rn w = 1, a valid answer like scipy's eigh gives there.
+    for (int e = tid; e < N * N; e += SOS_NT) C[e] = zmk(e / N == e % N ? 1.0 / N : 0.0, 0.0);
+    __syncthreads();
+  }
   zd* src = C;
   zd* dst = C2;
   for (int it = 0; it < GEV_SQUARINGS; it++) {
