@@ -153,6 +153,13 @@ SIGNATURES = {
     # EKF / IEKF tracking over the TDOA peaks: ExtendedKalmanFilter.next, KalmanFilter.update, IteratedExtendedKalmanFilter.update
     # (lib/pykalman.py:84-162, :199-266); the first argument points to an EkfParams
     "btk_ekf_track": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp, _vp, _vp]),
+    # ASR front end: PreemphasisFeature ... CepstralFeature (feature/feature.cc:1128-1144, :1177-1314, :1672-1792, :1892-2122,
+    # :2326-2415; matrix/gslmatrix.cc:107-131); the first argument of btk_fe_process points to an FeParams
+    "btk_fe_frames": (_l, [_l, _i, _i, _i]),
+    "btk_fe_process": (_i, [_vp, _vp, _vp]),
+    "btk_fe_mel_table": (_i, [_i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "btk_fe_vtln_table": (_i, [_i, _i, _d, _d, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "btk_fe_dct_table": (_i, [_i, _i, _i, _vp]),
 }
 
 
@@ -161,6 +168,15 @@ class EkfParams(C.Structure):
     _fields_ = [("n", _i), ("model", _i), ("type", _i), ("F", _d * 9), ("U", _d * 9), ("sigmaV2", _d), ("time_delta", _d),
                 ("gate_prob", _d), ("num_iterations", _i), ("iteration_threshold", _d), ("threshold", _d), ("minimum_pairs", _i),
                 ("Ts", _d), ("c", _d)]
+
+
+class FeParams(C.Structure):
+    """btk_fe_params of include/btkhip.h, field by field."""
+    _fields_ = [("S", _i), ("C", _i), ("T", _l), ("in_stage", _i), ("in_dim", _i), ("len", _l), ("pcm_stride", _l), ("D", _i),
+                ("shift", _i), ("L", _i), ("window", _i), ("preemph", _i), ("mu", _d), ("prior0", _vp), ("powN", _i),
+                ("vtlnN", _i), ("vtln_nw", _i), ("vtln_rows", _vp), ("vtln_w", _vp), ("melN", _i), ("mel_nw", _i),
+                ("mel_rows", _vp), ("mel_w", _vp), ("log_m", _d), ("log_a", _d), ("log_floor", _i), ("cepN", _i), ("dct", _vp),
+                ("out", _vp * 7)]
 
 
 def lib():

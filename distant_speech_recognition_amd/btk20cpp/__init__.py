@@ -148,6 +148,9 @@ _apply_signatures()
 # the reference exports every class under both names (X and XPtr, modulated.i:124-140 etc.)
 SampleFeature = _mod.SampleFeaturePtr
 HammingFeature, FFTFeature = _mod.HammingFeaturePtr, _mod.FFTFeaturePtr
+PreemphasisFeature, SpectralPowerFeature, VTLNFeature = _mod.PreemphasisFeaturePtr, _mod.SpectralPowerFeaturePtr, _mod.VTLNFeaturePtr
+MelFeature, LogFeature, CepstralFeature = _mod.MelFeaturePtr, _mod.LogFeaturePtr, _mod.CepstralFeaturePtr
+StorageFeature = _mod.StorageFeaturePtr
 OverSampledDFTAnalysisBank, OverSampledDFTSynthesisBank = _mod.OverSampledDFTAnalysisBankPtr, _mod.OverSampledDFTSynthesisBankPtr
 SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _mod.SubbandGSCRLSPtr
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
@@ -162,4 +165,5 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "SampleFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SubbandDS", "SubbandGSC", "SubbandGSCRLS",
             "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
             "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
-            "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature"]
+            "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
+            "LogFeature", "CepstralFeature", "StorageFeature"]

@@ -1679,3 +1679,175 @@ def ekf_track(lag, height, geom, params, state, t_begin=None):
                                    C.c_void_p(0) if t_begin is None else _ptr(t_begin), S, P, T, _ptr(state), _ptr(xk), _ptr(Kf),
                                    _ptr(flags), _stream()))
     return xk, Kf, flags
+
+
+# ---- ASR front end (btk_fe_*): PreemphasisFeature, HammingFeature + FFTFeature, SpectralPowerFeature, VTLNFeature, MelFeature,
+# LogFeature, CepstralFeature (feature/feature.cc:1128-1144, :1177-1314, :1672-1792, :1892-2122, :2326-2415) ---------------------
+FE_PCM, FE_SPECTRUM, FE_POWER, FE_VTLN, FE_MEL, FE_LOG, FE_CEP = range(7)
+FE_STAGES = ("pcm", "spectrum", "power", "vtln", "mel", "log", "cep")
+
+
+def _fe_stage(s):
+    if isinstance(s, str):
+        if s not in FE_STAGES:
+            raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "unknown front-end stage %r (one of %s)" % (s, ", ".join(FE_STAGES)))
+        return FE_STAGES.index(s)
+    return int(s)
+
+
+def fe_frames(nsamples, D, shift, pad_zeros=True):
+    """Frames of SampleFeature(block_len=D, shift_len=shift, pad_zeros=pad_zeros) over nsamples samples."""
+    return int(_lib.lib().btk_fe_frames(int(nsamples), int(D), int(shift), int(bool(pad_zeros))))
+
+
+class FeTable:
+    """A table of the front end: built once on the host (offset, count int32 [rows], coef packed row after row; a cosine table
+    is dense, count == cols), uploaded once per device and kept there."""
+
+    def __init__(self, offset, count, coef, cols):
+        self.offset, self.count, self.coef, self.cols = offset, count, coef, int(cols)
+        self.rows = int(offset.shape[0])
+        self.start = np.concatenate(([0], np.cumsum(count)[:-1])).astype(np.int32)
+        self._dev = {}
+
+    def matrix(self):
+        """The table as a dense float64 [rows][cols] matrix (MelFeature.matrix, VTLNFeature.matrix, CepstralFeature.matrix)."""
+        m = np.zeros((self.rows, self.cols), np.float64)
+        for j in range(self.rows):
+            m[j, self.offset[j]:self.offset[j] + self.count[j]] = self.coef[self.start[j]:self.start[j] + self.count[j]]
+        return m
+
+    def abs_column_sum(self):
+        """The largest absolute column sum: the table's gain on an l1 perturbation of its input."""
+        return float(np.abs(self.matrix()).sum(axis=0).max())
+
+    def on(self, device):
+        """(rows int32 [rows][3] = offset, count, start; coef) on the device."""
+        key = torch.device(device)
+        if key not in self._dev:
+            rows = np.ascontiguousarray(np.stack([self.offset, self.count, self.start], axis=1).astype(np.int32))
+            self._dev[key] = (torch.from_numpy(rows).to(key), torch.from_numpy(np.ascontiguousarray(self.coef)).to(key))
+        return self._dev[key]
+
+
+def fe_mel_table(powN, rate, low, up, filterN, version=1):
+    """MelFeature's band matrix (melScaleOrg: version 1, melScaleFF: version 2; feature/feature.cc:1904-2039), host code."""
+    powN, filterN = int(powN), int(filterN)
+    offset, count = np.zeros(max(filterN, 1), np.int32), np.zeros(max(filterN, 1), np.int32)
+    cap = max(filterN, 1) * max(powN, 1)
+    coef = np.zeros(cap, np.float32)
+    n = C.c_int(0)
+    check(_lib.lib().btk_fe_mel_table(powN, float(rate), float(low), float(up), filterN, int(version), _np_ptr(offset),
+                                      _np_ptr(count), _np_ptr(coef), cap, C.byref(n)))
+    return FeTable(offset, count, coef[:n.value].copy(), powN)
+
+
+def fe_vtln_table(N, ratio, edge=1.0, version=1, inN=None):
+    """VTLNFeature as an operator on the power vector (nextOrg: version 1, nextFF: version 2; feature/feature.cc:1672-1792),
+    float64 weights, host code."""
+    N = int(N)
+    inN = N if inN is None else int(inN)
+    offset, count = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32)
+    cap = max(N, 1) * max(inN, 1)
+    w = np.zeros(cap, np.float64)
+    n = C.c_int(0)
+    check(_lib.lib().btk_fe_vtln_table(N, inN, float(ratio), float(edge), int(version), _np_ptr(offset), _np_ptr(count),
+                                       _np_ptr(w), cap, C.byref(n)))
+    return FeTable(offset, count, w[:n.value].copy(), inN)
+
+
+def fe_dct_table(type, cepN, filterN):
+    """CepstralFeature's cosine table: types 0 and 1 of gsl_matrix_float_set_cosine (matrix/gslmatrix.cc:107-131), type 2 the
+    sphinx legacy form (feature/feature.cc:2389-2400); float32 [cepN][filterN], host code."""
+    cepN, filterN = int(cepN), int(filterN)
+    m = np.zeros((max(cepN, 1), max(filterN, 1)), np.float32)
+    check(_lib.lib().btk_fe_dct_table(int(type), cepN, filterN, _np_ptr(m)))
+    return FeTable(np.zeros(cepN, np.int32), np.full(cepN, filterN, np.int32), m.reshape(-1), filterN)
+
+
+def fe_process(x, in_stage="pcm", want=("cep",), D=None, shift=None, L=None, T=None, window=True, preemph=None, prior0=None,
+               powN=None, vtln=None, mel=None, log_m=1.0, log_a=1.0, log_floor=False, dct=None, nsamples=None, pad_zeros=True):
+    """The front end from the vectors of in_stage up to the last stage of `want`, one launch; -> {stage name: tensor} of the
+    wanted stages, float32 [S][C][T][dim] (spectrum: complex64 [S][C][T][L/2+1]).
+    in_stage "pcm": x float32 [S][C][len] or [S][len] (one channel; rows may be padded, as FilterBank.synthesize returns them):
+      frames of D samples every `shift` (default D), T frames (default fe_frames(len, D, shift, pad_zeros)), pre-emphasis with
+      mu = preemph where that is not None (prior0 float32 [S][C]: the sample before the first), Hamming window unless window is
+      False, transform length L.  in_stage "spectrum": x complex64 [S][C][T][L/2+1]; later stages: float32 [S][C][T][dim].
+    powN: L/2+1 (default) or L.  vtln, mel: FeTable or None (the stage is skipped); dct: FeTable of fe_dct_table."""
+    st = _fe_stage(in_stage)
+    wanted = sorted(set(_fe_stage(w) for w in ([want] if isinstance(want, (str, int)) else want)))
+    if not wanted or wanted[0] <= st or wanted[-1] > FE_CEP:
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "fe_process: the wanted stages must come after %s" % FE_STAGES[st])
+    if vtln is None:
+        wanted = [w for w in wanted if w != FE_VTLN]
+    if mel is None and st < FE_MEL:
+        wanted = [w for w in wanted if w != FE_MEL]
+    if not wanted:
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "fe_process: every wanted stage is skipped (no table given)")
+    q = _lib.FeParams()
+    q.in_stage = st
+    dev = x.device
+    if st == FE_PCM:
+        if x.dim() == 2:
+            x = x.unsqueeze(1)
+        if x.dtype != torch.float32 or x.dim() != 3 or not x.is_cuda or x.stride(2) != 1:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fe_process: pcm must be a float32 cuda tensor [S][C][len] with contiguous rows")
+        S, Cn, n = x.shape
+        stride = x.stride(1) if Cn > 1 else (x.stride(0) if S > 1 else max(n, 1))
+        if (Cn > 1 and S > 1 and x.stride(0) != Cn * stride) or stride < n:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fe_process: pcm rows must be evenly spaced")
+        if nsamples is not None and not 0 < int(nsamples) <= n:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fe_process: nsamples=%d outside the rows' %d samples" % (int(nsamples), n))
+        n = n if nsamples is None else int(nsamples)
+        if D is None or L is None:
+            raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "fe_process: D and L are needed from PCM")
+        D, L = int(D), int(L)
+        shift = D if shift is None else int(shift)
+        T = fe_frames(n, D, shift, pad_zeros) if T is None else int(T)
+        q.len, q.pcm_stride, q.D, q.shift, q.L, q.window = n, stride, D, shift, L, int(bool(window))
+        q.preemph, q.mu = int(preemph is not None), float(preemph or 0.0)
+        if prior0 is not None:
+            _check(prior0, "prior0", torch.float32, (S, Cn))
+            q.prior0 = prior0.data_ptr()
+        n_in = (L // 2 + 1) if powN is None else int(powN)
+    elif st == FE_SPECTRUM:
+        _check(x, "X", torch.complex64, 4)
+        S, Cn, T, K = x.shape
+        L = 2 * (K - 1)
+        q.L = L
+        n_in = (L // 2 + 1) if powN is None else int(powN)
+    else:
+        _check(x, FE_STAGES[st], torch.float32, 4)
+        S, Cn, T, n_in = x.shape
+        q.in_dim = n_in
+    q.S, q.C, q.T, q.powN = S, Cn, max(T, 0), n_in if st <= FE_SPECTRUM else 0
+    keep = []                                          # device tensors the launch reads
+    dims = {FE_SPECTRUM: (L // 2 + 1) if st <= FE_PCM else 0, FE_POWER: n_in}
+    n = n_in
+    last = wanted[-1]
+    if st < FE_VTLN and last >= FE_VTLN and vtln is not None:
+        rows, w = vtln.on(dev)
+        keep += [rows, w]
+        q.vtlnN, q.vtln_nw, q.vtln_rows, q.vtln_w = vtln.rows, int(w.numel()), rows.data_ptr(), w.data_ptr()
+        dims[FE_VTLN] = n = vtln.rows
+    if st < FE_MEL and last >= FE_MEL and mel is not None:
+        rows, w = mel.on(dev)
+        keep += [rows, w]
+        q.melN, q.mel_nw, q.mel_rows, q.mel_w = mel.rows, int(w.numel()), rows.data_ptr(), w.data_ptr()
+        dims[FE_MEL] = n = mel.rows
+    dims[FE_LOG] = n
+    q.log_m, q.log_a, q.log_floor = float(log_m), float(log_a), int(bool(log_floor))
+    if last >= FE_CEP:
+        if dct is None or dct.cols != n:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fe_process: cepstra need a cosine table over %d values" % n)
+        rows, w = dct.on(dev)
+        keep += [w]
+        q.cepN, q.dct = dct.rows, w.data_ptr()
+        dims[FE_CEP] = dct.rows
+    out = {}
+    for s in wanted:
+        t = torch.empty((S, Cn, max(T, 0), dims[s]), dtype=torch.complex64 if s == FE_SPECTRUM else torch.float32, device=dev)
+        out[FE_STAGES[s]] = t
+        q.out[s] = t.data_ptr()
+    check(_lib.lib().btk_fe_process(C.cast(C.pointer(q), C.c_void_p), _ptr(x), _stream()))
+    return out

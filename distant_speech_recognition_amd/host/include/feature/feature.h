@@ -13,6 +13,8 @@ enum { SF_FORMAT_WAV = 0x010000, SF_FORMAT_PCM_16 = 0x0002 };
 }
 
 class SampleFeature;
+class PreemphasisFeature;
+class StorageFeature;
 typedef Inherit<SampleFeature, VectorFloatFeatureStreamPtr> SampleFeaturePtr;
 
 class SampleFeature : public VectorFloatFeatureStream {
@@ -120,7 +122,19 @@ class FFTFeature : public VectorComplexFeatureStream {
   long pull_sample_blocks(float* dst, long nmax);
   // launches this node has made since it was built (tests)
   long launches() const { return launches_; }
+  // engine hooks of the front-end nodes (SpectralPowerFeature and above): whether this node stands over a HammingFeature over
+  // [a PreemphasisFeature over] [a StorageFeature over] a SampleFeature (blocks may overlap), then up to nmax of the
+  // SampleFeature's blocks back to back in dst with the state transitions of as many next() calls on every node BELOW this
+  // one, the pre-emphasis the kernel has to apply, and this node's own transition once the block's last half spectrum is known
+  bool has_fe_chain() const { return fe_sample_ != NULL; }
+  long pull_fe_blocks(float* dst, long nmax, int* preemph, double* mu, float* prior0);
+  void fe_advance(long n, const float* last_half);
  private:
+  void find_fe_chain_();
+  HammingFeature* fe_hamming_;
+  PreemphasisFeature* fe_preemph_;
+  StorageFeature* fe_storage_;
+  SampleFeature* fe_sample_;
   void fill_block_();
   void serve_(const float* half);
   VectorFloatFeatureStreamPtr samp_;
@@ -132,3 +146,194 @@ class FFTFeature : public VectorComplexFeatureStream {
   DeviceBuffer d_in_, d_out_, d_energy_;
 };
 typedef Inherit<FFTFeature, VectorComplexFeatureStreamPtr> FFTFeaturePtr;
+
+// ================================================================================================ the recogniser's front end
+// PreemphasisFeature, SpectralPowerFeature, VTLNFeature, MelFeature, LogFeature, CepstralFeature, StorageFeature (reference
+// feature/feature.h:436-455, :548-555, :640-672, :835-905, :961-978, :986-1003, :1196-1222; feature/feature.cc:1113-1144, :1291-1314,
+// :1662-1850, :1892-2242, :2326-2428, :2905-2996) over btk_fe_process (csrc/fe_kernels.hip).
+//
+// PreemphasisFeature and StorageFeature are host nodes (node boundaries, like HammingFeature).  The nodes from the power
+// spectrum up serve BLOCKS where their sources lead, through nodes of these classes, down to an FFTFeature over a
+// HammingFeature over [a PreemphasisFeature over] [a StorageFeature over] a SampleFeature: the first next() of a block pulls
+// up to block_frames sample blocks, launches btk_fe_process once from PCM up to the node's own stage (the sample blocks back to
+// back, shift = D at the ABI, also where the SampleFeature's blocks overlap) and serves the frames from a pinned host copy;
+// every node of the chain below makes the state transitions of as many next() calls (its vector is the block's last frame).
+// Over any other source a node uploads the one frame the source hands out and enters the kernel at its own stage.
+// Construction touches no device: tables are built on the host and uploaded with the first launch.
+class PreemphasisFeature : public VectorFloatFeatureStream {
+ public:
+  PreemphasisFeature(const VectorFloatFeatureStreamPtr& samp, double mu = 0.95, const String& nm = "Preemphasis");
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { samp_->reset(); VectorFloatFeatureStream::reset(); }
+  void next_speaker() { prior_ = 0.0f; }
+  void nextSpeaker() { next_speaker(); }
+  // engine hooks: the source, mu, the sample before the next one, and the state transitions of n next() calls over n
+  // blocks stored back to back
+  VectorFloatFeatureStreamPtr& source() { return samp_; }
+  double mu() const { return mu_; }
+  float prior() const { return prior_; }
+  const float* current_vector() const { return vector_->data; }
+  void advance_blocks(long n, const float* blocks);
+ private:
+  VectorFloatFeatureStreamPtr samp_;
+  float prior_;
+  double mu_;
+};
+typedef Inherit<PreemphasisFeature, VectorFloatFeatureStreamPtr> PreemphasisFeaturePtr;
+
+class StorageFeature : public VectorFloatFeatureStream {
+ public:
+  static const int MaxFrames = 100000;
+  StorageFeature(const VectorFloatFeatureStreamPtr& src, const String& nm = "Storage");
+  virtual ~StorageFeature();
+  // a stored frame for 0 <= frame_no <= the last one, the source's next frame otherwise (feature.cc:2920-2934)
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { src_->reset(); VectorFloatFeatureStream::reset(); }
+  void write(const String& fileName, bool plainText = false) const;
+  void read(const String& fileName);
+  int evaluate();
+  VectorFloatFeatureStreamPtr& source() { return src_; }
+  void store_blocks(long n, const float* blocks);      // engine hook: n next() calls whose source blocks lie back to back
+ private:
+  gsl_vector_float* frame_(int i);
+  VectorFloatFeatureStreamPtr src_;
+  std::vector<gsl_vector_float*> frames_;              // allocated as they are filled
+};
+typedef Inherit<StorageFeature, VectorFloatFeatureStreamPtr> StorageFeaturePtr;
+
+struct btk_fe_params;
+
+// what the nodes from POWER up share: the wiring of a chain and the block service
+class FeStageNode {
+ public:
+  virtual ~FeStageNode() {}
+  int fe_stage() const { return stage_; }
+  long launches() const { return launches_; }          // launches this node has made since it was built (tests)
+  long block_frames() const { return block_frames_; }
+  void set_block_frames(long n);
+ protected:
+  FeStageNode(int stage);
+  void fe_wire_(FeStageNode* below, FFTFeature* fft);  // the source, where it is a node of these classes or an FFTFeature
+  const float* fe_next_();                             // this node's next frame, float32 [fe_dim()]
+  void fe_reset_() { blk_n_ = blk_pos_ = 0; }
+  void fe_tables_changed_() { tables_dirty_ = true; }
+  virtual unsigned fe_dim() const = 0;
+  virtual void fe_params(btk_fe_params& q) = 0;        // the node's own tables and constants (device copies made here)
+  virtual void fe_advance(long n, const float* last) = 0;
+  // one frame of a source that is no chain: its values as float32 (complex64 pairs for a spectrum), the stage they are of
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L) = 0;
+  // a table as the kernel reads it
+  void fe_upload_(DeviceBuffer& d, const void* h, size_t bytes);
+  bool tables_dirty_;
+ public:
+  FeStageNode* fe_below() const { return below_; }
+ private:
+  FFTFeature* root_() const;
+  void fill_chain_(FFTFeature* root);
+  void fill_single_();
+  int stage_;
+  FeStageNode* below_;
+  FFTFeature* fft_;
+  long block_frames_, blk_n_, blk_pos_, launches_;
+  PinnedBuffer h_in_, h_out_, h_last_;
+  DeviceBuffer d_in_, d_out_, d_prior_;
+};
+
+class SpectralPowerFeature : public VectorFeatureStream, public FeStageNode {
+ public:
+  SpectralPowerFeature(const VectorComplexFeatureStreamPtr& fft, unsigned powN = 0, const String& nm = "Power");
+  virtual const gsl_vector* next(int frame_no = -5);
+  virtual void reset() { fft_->reset(); VectorFeatureStream::reset(); fe_reset_(); }
+ protected:
+  virtual unsigned fe_dim() const { return size(); }
+  virtual void fe_params(btk_fe_params& q);
+  virtual void fe_advance(long n, const float* last);
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L);
+ private:
+  VectorComplexFeatureStreamPtr fft_;
+};
+typedef Inherit<SpectralPowerFeature, VectorFeatureStreamPtr> SpectralPowerFeaturePtr;
+
+class VTLNFeature : public VectorFeatureStream, public FeStageNode {
+ public:
+  VTLNFeature(const VectorFeatureStreamPtr& pow, unsigned coeffN = 0, double ratio = 1.0, double edge = 1.0, int version = 1,
+              const String& nm = "VTLN");
+  virtual const gsl_vector* next(int frame_no = -5);
+  virtual void reset() { pow_->reset(); VectorFeatureStream::reset(); fe_reset_(); }
+  void warp(double w);                                 // frames served after the call use the new ratio
+  void matrix(gsl_matrix* mat) const;                  // the warp as a size() x source_size() operator on the power vector
+  unsigned source_size() const { return pow_->size(); }
+ protected:
+  virtual unsigned fe_dim() const { return size(); }
+  virtual void fe_params(btk_fe_params& q);
+  virtual void fe_advance(long n, const float* last);
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L);
+ private:
+  void build_();
+  VectorFeatureStreamPtr pow_;
+  double ratio_, edge_;
+  int version_;
+  std::vector<int> rows_;                              // [size()][3]: offset, count, start
+  std::vector<double> w_;
+  DeviceBuffer d_rows_, d_w_;
+};
+typedef Inherit<VTLNFeature, VectorFeatureStreamPtr> VTLNFeaturePtr;
+
+class MelFeature : public VectorFeatureStream, public FeStageNode {
+ public:
+  MelFeature(const VectorFeatureStreamPtr& mag, int powN = 0, float rate = 16000.0, float low = 0.0, float up = 0.0,
+             unsigned filterN = 30, unsigned version = 1, const String& nm = "MelFFT");
+  virtual const gsl_vector* next(int frame_no = -5);
+  virtual void reset() { mag_->reset(); VectorFeatureStream::reset(); fe_reset_(); }
+  void read(const String& fileName);                   // band matrices from a file are not carried over: jio_error
+  void matrix(gsl_matrix* mat) const;                  // filterN x powN
+  unsigned powN() const { return powN_; }
+ protected:
+  virtual unsigned fe_dim() const { return size(); }
+  virtual void fe_params(btk_fe_params& q);
+  virtual void fe_advance(long n, const float* last);
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L);
+ private:
+  VectorFeatureStreamPtr mag_;
+  unsigned powN_;
+  std::vector<int> rows_;
+  std::vector<float> w_;
+  DeviceBuffer d_rows_, d_w_;
+};
+typedef Inherit<MelFeature, VectorFeatureStreamPtr> MelFeaturePtr;
+
+class LogFeature : public VectorFloatFeatureStream, public FeStageNode {
+ public:
+  LogFeature(const VectorFeatureStreamPtr& mel, double m = 1.0, double a = 1.0, bool sphinxFlooring = false,
+             const String& nm = "LogMel");
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { mel_->reset(); VectorFloatFeatureStream::reset(); fe_reset_(); }
+ protected:
+  virtual unsigned fe_dim() const { return size(); }
+  virtual void fe_params(btk_fe_params& q);
+  virtual void fe_advance(long n, const float* last);
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L);
+ private:
+  VectorFeatureStreamPtr mel_;
+  double m_, a_;
+  bool floor_;
+};
+typedef Inherit<LogFeature, VectorFloatFeatureStreamPtr> LogFeaturePtr;
+
+class CepstralFeature : public VectorFloatFeatureStream, public FeStageNode {
+ public:
+  CepstralFeature(const VectorFloatFeatureStreamPtr& mel, unsigned ncep = 13, int type = 1, const String& nm = "Cepstral");
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { mel_->reset(); VectorFloatFeatureStream::reset(); fe_reset_(); }
+  gsl_matrix* matrix() const;                          // a new ncep x mel->size() matrix (the caller frees it)
+ protected:
+  virtual unsigned fe_dim() const { return size(); }
+  virtual void fe_params(btk_fe_params& q);
+  virtual void fe_advance(long n, const float* last);
+  virtual void fe_pull_one(std::vector<float>& in, int& in_stage, int& in_dim, int& L);
+ private:
+  VectorFloatFeatureStreamPtr mel_;
+  std::vector<float> cos_;
+  DeviceBuffer d_cos_;
+};
+typedef Inherit<CepstralFeature, VectorFloatFeatureStreamPtr> CepstralFeaturePtr;

@@ -3948,6 +3948,7 @@ FFTFeature::FFTFeature(const VectorFloatFeatureStreamPtr& samp, unsigned fftLen,
   // overlapping blocks (shiftLen != blockLen) are no frames of one signal: they go frame by frame
   if (sample_ && sample_->shiftlen() != sample_->size()) sample_ = NULL;
   if (!sample_) hamming_ = NULL;
+  find_fe_chain_();
 }
 
 void FFTFeature::set_block_frames(long n)

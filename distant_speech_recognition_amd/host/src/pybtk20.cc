@@ -83,6 +83,7 @@ struct GslCMat {
 
 // views of node-owned storage (kept alive by `owner`), copies of transient views
 py::array view(const gsl_vector_float* v, py::handle owner) { return py::array_t<float>({(py::ssize_t)v->size}, {(py::ssize_t)sizeof(float)}, v->data, owner); }
+py::array view(const gsl_vector* v, py::handle owner) { return py::array_t<double>({(py::ssize_t)v->size}, {(py::ssize_t)sizeof(double)}, v->data, owner); }
 py::array view(const gsl_vector_complex* v, py::handle owner) { return py::array_t<cd>({(py::ssize_t)v->size}, {(py::ssize_t)sizeof(cd)}, reinterpret_cast<const cd*>(v->data), owner); }
 py::array copy_of(const gsl_vector_complex* v) {
   py::array_t<cd> a((py::ssize_t)v->size);
@@ -164,6 +165,7 @@ class PyStream : public Base, public BlockSource {
 };
 typedef PyStream<VectorFloatFeatureStream, gsl_vector_float, float> PyVectorFloatFeatureStream;
 typedef PyStream<VectorComplexFeatureStream, gsl_vector_complex, cd> PyVectorComplexFeatureStream;
+typedef PyStream<VectorFeatureStream, gsl_vector, double> PyVectorFeatureStream;
 
 // the methods of DOAEstimatorSRPBase (beamformer.i:677-708) on a bound class T that derives from it.  nbest_rps / nbest_doas /
 // response_power_matrix are numpy VIEWS of the estimator's own storage (kept alive by the array), like next()'s vector.
@@ -209,6 +211,28 @@ VectorFloatFeatureStreamPtr as_fstream(const py::object& o)
 {
   if (py::isinstance<VectorFloatFeatureStream>(o)) return VectorFloatFeatureStreamPtr(o.cast<VectorFloatFeatureStream*>());
   return VectorFloatFeatureStreamPtr(new PyVectorFloatFeatureStream(o, "PyVectorFloatFeatureStream"));
+}
+VectorFeatureStreamPtr as_dstream(const py::object& o)
+{
+  if (py::isinstance<VectorFeatureStream>(o)) return VectorFeatureStreamPtr(o.cast<VectorFeatureStream*>());
+  return VectorFeatureStreamPtr(new PyVectorFeatureStream(o, "PyVectorFeatureStream"));
+}
+py::array dense_of(gsl_matrix* m)
+{
+  py::array_t<double> a({(py::ssize_t)m->size1, (py::ssize_t)m->size2});
+  for (size_t i = 0; i < m->size1; i++) memcpy(a.mutable_data(i, 0), m->data + i * m->tda, sizeof(double) * m->size2);
+  return std::move(a);
+}
+// matrix(matrix): the reference fills the caller's matrix; here the dense matrix is returned, and copied into `out` where one is given
+template <class T>
+py::array matrix_of(T& node, size_t rows, size_t cols, py::object out)
+{
+  gsl_matrix* m = gsl_matrix_alloc(rows, cols);
+  try { node.matrix(m); } catch (...) { gsl_matrix_free(m); throw; }
+  py::array a = dense_of(m);
+  gsl_matrix_free(m);
+  if (!out.is_none()) out.attr("__setitem__")(py::ellipsis(), a);
+  return a;
 }
 py::array block_of(BlockSource& b)
 {
@@ -270,6 +294,8 @@ PYBIND11_MODULE(_btk20cpp, m)
   // ---- stream bases
   py::class_<VectorFloatFeatureStream, cref<VectorFloatFeatureStream>> vf(m, "VectorFloatFeatureStream");
   bind_stream_methods<VectorFloatFeatureStream>(vf);
+  py::class_<VectorFeatureStream, cref<VectorFeatureStream>> vd(m, "VectorFeatureStream");
+  bind_stream_methods<VectorFeatureStream>(vd);
   py::class_<VectorComplexFeatureStream, cref<VectorComplexFeatureStream>> vc(m, "VectorComplexFeatureStream");
   bind_stream_methods<VectorComplexFeatureStream>(vc);
 
@@ -344,6 +370,73 @@ PYBIND11_MODULE(_btk20cpp, m)
              py::array_t<float> a({(py::ssize_t)n, (py::ssize_t)f.windowLen()});
              if (n > 0) memcpy(a.mutable_data(), buf.data(), sizeof(float) * (size_t)n * f.windowLen());
              return a; }, py::arg("nmax"));
+
+  // the recogniser's front end (feature/feature.i: PreemphasisFeature, SpectralPowerFeature, VTLNFeature, MelFeature, LogFeature,
+  // CepstralFeature, StorageFeature); block_frames / set_block_frames / launches are the engine's additions
+  py::class_<PyVectorFeatureStream, VectorFeatureStream, cref<PyVectorFeatureStream>>(m, "PyVectorFeatureStreamPtr")
+      .def(py::init([](py::object c, const std::string& nm) { return new PyVectorFeatureStream(c, nm); }), py::arg("c"), py::arg("nm") = "PyVectorFeatureStream")
+      .def("python_object", &PyVectorFeatureStream::python_object);
+  py::class_<PreemphasisFeature, VectorFloatFeatureStream, cref<PreemphasisFeature>>(m, "PreemphasisFeaturePtr")
+      .def(py::init([](py::object samp, double mu, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             return new PreemphasisFeature(sp, mu, nm);
+           }), py::arg("samp"), py::arg("mu") = 0.95, py::arg("nm") = "Preemphasis")
+      .def("next_speaker", &PreemphasisFeature::next_speaker)
+      .def("nextSpeaker", &PreemphasisFeature::next_speaker);
+  py::class_<StorageFeature, VectorFloatFeatureStream, cref<StorageFeature>>(m, "StorageFeaturePtr")
+      .def(py::init([](py::object src, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(src);
+             return new StorageFeature(sp, nm);
+           }), py::arg("src"), py::arg("nm") = "Storage")
+      .def("write", [](StorageFeature& s, const std::string& fn, bool plainText) { s.write(fn, plainText); }, py::arg("fileName"), py::arg("plainText") = false)
+      .def("read", [](StorageFeature& s, const std::string& fn) { s.read(fn); }, py::arg("fileName"))
+      .def("evaluate", &StorageFeature::evaluate);
+  py::class_<SpectralPowerFeature, VectorFeatureStream, cref<SpectralPowerFeature>>(m, "SpectralPowerFeaturePtr")
+      .def(py::init([](py::object fft, unsigned pow_num, const std::string& nm) {
+             VectorComplexFeatureStreamPtr sp = as_cstream(fft);
+             return new SpectralPowerFeature(sp, pow_num, nm);
+           }), py::arg("fft"), py::arg("pow_num") = 0, py::arg("nm") = "Power")
+      .def("set_block_frames", [](SpectralPowerFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](SpectralPowerFeature& f) { return f.block_frames(); })
+      .def("launches", [](SpectralPowerFeature& f) { return f.launches(); });
+  py::class_<VTLNFeature, VectorFeatureStream, cref<VTLNFeature>>(m, "VTLNFeaturePtr")
+      .def(py::init([](py::object pow, unsigned coeff_num, double ratio, double edge, int version, const std::string& nm) {
+             VectorFeatureStreamPtr sp = as_dstream(pow);
+             return new VTLNFeature(sp, coeff_num, ratio, edge, version, nm);
+           }), py::arg("pow"), py::arg("coeff_num") = 0, py::arg("ratio") = 1.0, py::arg("edge") = 1.0, py::arg("version") = 1, py::arg("nm") = "VTLN")
+      .def("warp", &VTLNFeature::warp, py::arg("w"))
+      .def("matrix", [](VTLNFeature& f, py::object out) { return matrix_of(f, f.size(), f.source_size(), out); }, py::arg("matrix") = py::none())
+      .def("set_block_frames", [](VTLNFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](VTLNFeature& f) { return f.block_frames(); })
+      .def("launches", [](VTLNFeature& f) { return f.launches(); });
+  py::class_<MelFeature, VectorFeatureStream, cref<MelFeature>>(m, "MelFeaturePtr")
+      .def(py::init([](py::object mag, int pow_num, float rate, float low, float up, unsigned filter_num, unsigned version, const std::string& nm) {
+             VectorFeatureStreamPtr sp = as_dstream(mag);
+             return new MelFeature(sp, pow_num, rate, low, up, filter_num, version, nm);
+           }), py::arg("mag"), py::arg("pow_num") = 0, py::arg("rate") = 16000.0f, py::arg("low") = 0.0f, py::arg("up") = 0.0f,
+           py::arg("filter_num") = 30, py::arg("version") = 1, py::arg("nm") = "MelFFT")
+      .def("read", [](MelFeature& f, const std::string& fn) { f.read(fn); }, py::arg("fileName"))
+      .def("matrix", [](MelFeature& f, py::object out) { return matrix_of(f, f.size(), f.powN(), out); }, py::arg("matrix") = py::none())
+      .def("set_block_frames", [](MelFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](MelFeature& f) { return f.block_frames(); })
+      .def("launches", [](MelFeature& f) { return f.launches(); });
+  py::class_<LogFeature, VectorFloatFeatureStream, cref<LogFeature>>(m, "LogFeaturePtr")
+      .def(py::init([](py::object mel, double mm, double a, bool sphinxFlooring, const std::string& nm) {
+             VectorFeatureStreamPtr sp = as_dstream(mel);
+             return new LogFeature(sp, mm, a, sphinxFlooring, nm);
+           }), py::arg("mel"), py::arg("m") = 1.0, py::arg("a") = 1.0, py::arg("sphinxFlooring") = false, py::arg("nm") = "LogMel")
+      .def("set_block_frames", [](LogFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](LogFeature& f) { return f.block_frames(); })
+      .def("launches", [](LogFeature& f) { return f.launches(); });
+  py::class_<CepstralFeature, VectorFloatFeatureStream, cref<CepstralFeature>>(m, "CepstralFeaturePtr")
+      .def(py::init([](py::object mel, unsigned ncep, int type, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(mel);
+             return new CepstralFeature(sp, ncep, type, nm);
+           }), py::arg("mel"), py::arg("ncep") = 13, py::arg("type") = 1, py::arg("nm") = "Cepstral")
+      .def("matrix", [](CepstralFeature& f) { gsl_matrix* mm = f.matrix(); py::array a = dense_of(mm); gsl_matrix_free(mm); return a; })
+      .def("set_block_frames", [](CepstralFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](CepstralFeature& f) { return f.block_frames(); })
+      .def("launches", [](CepstralFeature& f) { return f.launches(); });
 
   // ---- modulated/modulated.h
   py::class_<OverSampledDFTAnalysisBank, VectorComplexFeatureStream, cref<OverSampledDFTAnalysisBank>>(m, "OverSampledDFTAnalysisBankPtr")

@@ -649,6 +649,88 @@ typedef struct btk_ekf_params {
 int  btk_ekf_track(const btk_ekf_params* params, const void* lag, const void* height, const void* geom, const void* t_begin,
                    int S, int P, long T, void* state, void* xk, void* Kf, void* flags, void* stream);
 
+/* ---- ASR front end: the nodes of unit_test/log_power_extractor.py and unit_test/mfcc_extractor.py --------------------------
+ * Stages: PCM(0) -> SPECTRUM(1) -> POWER(2) -> VTLN(3) -> MEL(4) -> LOG(5) -> CEP(6).  btk_fe_process takes the vectors of stage
+ * in_stage and runs the stages after it, up to the last one whose out[] pointer is non-NULL; VTLN is skipped where vtln_rows is
+ * NULL, MEL where mel_rows is NULL.  Every requested stage is written: out[stage] [dev] float32 [S][C][T][dim] (SPECTRUM:
+ * complex64 [S][C][T][L/2+1]); out[0] is unused.
+ *
+ * PCM (PreemphasisFeature::next, feature/feature.cc:1128-1144; HammingFeature::next + FFTFeature::next, :1177-1258):
+ *   in [dev] float32 [S][C] rows of len samples, pcm_stride apart.  Frame t covers samples t shift .. t shift + D - 1, zero at and
+ *   beyond len; 1 <= shift <= D <= L, T frames (btk_fe_frames gives SampleFeature's count).  preemph != 0: sample i becomes
+ *   float(x_i - mu prior) with the difference in float64; the prior is the sample before it, for the first sample of frame t > 0
+ *   the LAST sample of frame t - 1 (sample (t-1) shift + D - 1, the reference's prior_, also when frames overlap), for t = 0
+ *   prior0 [dev] float32 [S][C] (NULL: zero).  window as btk_tdoa_spectra (float64 product rounded to float32), zero padding to L,
+ *   forward transform, unnormalised.  L a power of two from 256 to 16384.  With window HAMMING, no pre-emphasis and shift = D
+ *   the spectra have the bits of btk_tdoa_spectra.
+ * POWER (SpectralPowerFeature::next, :1291-1314): |X_k|^2, k < powN, powN = L/2+1 or L (upper half: the conjugate mirror).
+ * VTLN (VTLNFeature::nextOrg / nextFF, :1672-1792), MEL (MelFeature::next over fmatrixBMulot, :2055-2109, :2229-2242),
+ * CEP (CepstralFeature::next, :2402-2415): a table applied to the previous stage, accumulated in float64, rounded to float32.
+ *   *_rows [dev] int32 [N][3]: (first input index, coefficient count, index of the row's first coefficient in *_w)
+ *   vtln_w [dev] float64, mel_w [dev] float32 packed row after row;  dct [dev] float32 [cepN][dimension of LOG], dense.
+ *   Coefficients that would read past the input vector are ignored.
+ * LOG (LogFeature::next, :2332-2362): float(log_m log10(v + log_a)) with v + log_a <= 0 -> 1.0, or with log_floor != 0
+ *   v < 1e-5 -> 1e-5 and log_a unused; evaluated in float64 on the float32 input.
+ * The tables are the caller's: a coefficient that would read past the input vector or past *_nw is ignored, nothing else of a
+ * table is checked.  Entering at SPECTRUM or later no stage may be longer than 20480 values (BTK_ERR_DIMENSION).
+ * in_stage >= POWER: in_dim is the length of the input vectors (any >= 1) and the PCM fields are unused; in_stage == SPECTRUM:
+ * in [dev] complex64 [S][C][T][L/2+1].  With in_stage PCM the stage lengths after POWER may not exceed L/2+1 (vtlnN: powN).
+ * BTK_ERR_DIMENSION for L, D, shift, powN or a stage length outside these ranges, BTK_ERR_PARAMETER for a null input, an unknown
+ * stage or window, or no requested output; nothing is launched.                                                              */
+#define BTK_FE_PCM 0
+#define BTK_FE_SPECTRUM 1
+#define BTK_FE_POWER 2
+#define BTK_FE_VTLN 3
+#define BTK_FE_MEL 4
+#define BTK_FE_LOG 5
+#define BTK_FE_CEP 6
+typedef struct btk_fe_params {
+  int S, C;
+  long T;
+  int in_stage, in_dim;
+  long len, pcm_stride;
+  int D, shift, L, window, preemph;
+  double mu;
+  const float* prior0;
+  int powN;
+  int vtlnN, vtln_nw;          /* rows, packed weights */
+  const int* vtln_rows;
+  const double* vtln_w;
+  int melN, mel_nw;
+  const int* mel_rows;
+  const float* mel_w;
+  double log_m, log_a;
+  int log_floor;
+  int cepN;
+  const float* dct;
+  void* out[7];
+} btk_fe_params;
+/* frames of SampleFeature(block_len = D, shift_len = shift) over len samples (feature/feature.cc:1050-1108): every start
+ * t shift < len with pad_zeros, every start with t shift + D <= len without                                                  */
+long btk_fe_frames(long len, int D, int shift, int pad_zeros);
+int  btk_fe_process(const btk_fe_params* params, const void* in, void* stream);
+/* Host code, no device.  MelFeature::SparseMatrix_::melScaleOrg (version 1) / melScaleFF (version 2), feature/feature.cc:1892-2039
+ * with the constructor's up <= 0 -> rate / 2 (:2199-2208), every float of the reference a float32 here:
+ *   offset [host] int32 [filterN], count [host] int32 [filterN], coef [host] float32 [coef_cap] packed row after row,
+ *   *ncoef: coefficients written.  Version 1 advances the frequency before the coefficient (negative coefficients are kept).
+ * BTK_ERR_PARAMETER for low < 0, 2 up > rate, low > up (the reference's j_error) or a version other than 1 and 2;
+ * BTK_ERR_DIMENSION for a row with offset + count > powN, a negative count or more than coef_cap coefficients.                 */
+int  btk_fe_mel_table(int powN, float rate, float low, float up, int filterN, int version, int* offset, int* count,
+                      float* coef, int coef_cap, int* ncoef);
+/* VTLNFeature::nextOrg (version 1) / nextFF (version 2), feature/feature.cc:1672-1792, as the operator W [N][inN] on the power
+ * vector, out_k = sum_s W[k][s] in_s.  Version 1: the interpolation weights alpha0, ones, alpha1 with the index clamps of
+ * :1703-1707.  Version 2 (inN == N): the scatter weights with float32 b, slope1, slope2, sIdx -+ 0.5, dIdx, the k < 0 -> 0 clamp
+ * and the k >= N break, each row divided by its normaliser auxV_ where that exceeds 1e-20 (at ratio 1 a normalised
+ * [1/2, 1, 1/2] smoothing, not the identity).
+ *   offset, count [host] int32 [N]: the span of each row's non-zero weights;  w [host] float64 [w_cap] packed;  *nw: weights written
+ * BTK_ERR_PARAMETER for another version, BTK_ERR_DIMENSION for N, inN < 1, version 2 with inN != N or more than w_cap weights.  */
+int  btk_fe_vtln_table(int N, int inN, double ratio, double edge, int version, int* offset, int* count, double* w, int w_cap,
+                       int* nw);
+/* gsl_matrix_float_set_cosine types 0 and 1 (matrix/gslmatrix.cc:107-131) and type 2, CepstralFeature::sphinxLegacy_
+ * (feature/feature.cc:2389-2400): dct [host] float32 [cepN][filterN], computed in float64 and rounded.
+ * BTK_ERR_PARAMETER for another type, BTK_ERR_DIMENSION for cepN, filterN < 1 (type 0: filterN < 2).                           */
+int  btk_fe_dct_table(int type, int cepN, int filterN, float* dct);
+
 #ifdef __cplusplus
 }
 #endif

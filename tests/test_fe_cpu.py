@@ -1,0 +1,200 @@
+"""CPU: the table entries of the ASR front end (btk_fe_mel_table, btk_fe_vtln_table, btk_fe_dct_table, btk_fe_frames) are host
+code and equal the numpy restatement of the reference (tests/fe_closed_form.py) bit for bit."""
+import numpy as np
+import pytest
+
+from tests import fe_closed_form as cf
+
+MEL_CASES = [(129, 16000, 100, 6800, 30), (257, 16000, 0, 0, 40), (17, 16000, 0, 8000, 6), (17, 16000, 0, 8000, 12)]
+
+
+@pytest.fixture(scope="module")
+def engine():
+    from distant_speech_recognition_amd import engine
+    return engine
+
+
+@pytest.mark.parametrize("version", [1, 2])
+@pytest.mark.parametrize("case", MEL_CASES)
+def test_mel_table_bit_equal(engine, case, version):
+    powN, rate, low, up, filterN = case
+    t = engine.fe_mel_table(powN, rate, low, up, filterN, version)
+    off, cnt, rows = cf.mel_table(powN, rate, low, up, filterN, version)
+    assert np.array_equal(t.offset, off) and np.array_equal(t.count, cnt)
+    assert t.coef.dtype == np.float32 and np.array_equal(t.coef, np.concatenate(rows))
+    assert np.all(t.offset + t.count <= powN) and t.cols == powN and t.rows == filterN
+    assert np.array_equal(t.start, np.concatenate(([0], np.cumsum(cnt)[:-1])))
+
+
+def test_mel_table_properties(engine):
+    # 12 filters over 17 bins: one-coefficient filters and repeated offsets
+    t = engine.fe_mel_table(17, 16000, 0, 8000, 12, 2)
+    assert list(t.offset[:6]) == [0, 1, 1, 2, 2, 3] and t.count.min() == 1
+    # version 1 advances the frequency before the coefficient: the last coefficient of a filter may lie past its right edge
+    t1 = engine.fe_mel_table(129, 16000, 100, 6800, 30, 1)
+    t2 = engine.fe_mel_table(129, 16000, 100, 6800, 30, 2)
+    print("min coefficient: version 1 %g, version 2 %g" % (t1.coef.min(), t2.coef.min()))
+    assert -0.01 < t1.coef.min() < -0.008 and t2.coef.min() >= 0.0
+    assert 2 <= t1.count.min() and t1.count.max() <= 16
+    m = t2.matrix()
+    assert m.shape == (30, 129) and m[3, t2.offset[3]] == np.float64(t2.coef[t2.start[3]])
+
+
+def test_mel_table_refusals(engine):
+    from distant_speech_recognition_amd import _lib
+    for low, up in ((-1.0, 6800.0), (100.0, 8001.0), (7000.0, 6800.0)):       # low < 0, 2 up > rate, low > up
+        with pytest.raises(_lib.BtkError) as e:
+            engine.fe_mel_table(129, 16000, low, up, 30, 1)
+        assert e.value.code == _lib.BTK_ERR_PARAMETER
+    with pytest.raises(_lib.BtkError) as e:
+        engine.fe_mel_table(129, 16000, 100, 6800, 30, 3)
+    assert e.value.code == _lib.BTK_ERR_PARAMETER
+    # 16 bins spaced rate / 32 with the upper edge at rate / 2 (6000 Hz survives the float32 round trip through the mel scale):
+    # the last filter ends at bin 16, one past the vector
+    with pytest.raises(_lib.BtkError) as e:
+        engine.fe_mel_table(16, 12000, 0, 0, 6, 1)
+    assert e.value.code == _lib.BTK_ERR_DIMENSION
+    with pytest.raises(ValueError):
+        cf.mel_table(129, 16000, 100, 8001, 30, 1)
+
+
+@pytest.mark.parametrize("version", [1, 2])
+@pytest.mark.parametrize("edge", [0.8, 1.0])
+@pytest.mark.parametrize("ratio", [0.88, 1.0, 1.12])
+def test_vtln_table_bit_equal(engine, ratio, edge, version):
+    N = 33
+    t = engine.fe_vtln_table(N, ratio, edge, version)
+    assert t.coef.dtype == np.float64
+    assert np.array_equal(t.matrix(), cf.vtln_matrix(N, N, ratio, edge, version))
+
+
+def test_vtln_version1_identity_at_ratio_one(engine):
+    # X0 = (c / N) N is c up to one rounding, so a weight may move 1e-14 to the neighbouring bin: the identity to that precision
+    for edge in (0.8, 1.0):
+        m = engine.fe_vtln_table(129, 1.0, edge, 1).matrix()
+        assert np.max(np.abs(m - np.eye(129))) < 1e-12
+    assert np.array_equal(engine.fe_vtln_table(32, 1.0, 1.0, 1).matrix(), np.eye(32))       # a power of two: exact
+
+
+def test_vtln_version2_smoothing_at_ratio_one(engine):
+    N = 17
+    m = engine.fe_vtln_table(N, 1.0, 1.0, 2).matrix()
+    want = np.zeros((N, N))
+    for k in range(1, N - 1):
+        want[k, k - 1:k + 2] = [0.25, 0.5, 0.25]                   # [1/2, 1, 1/2] over its sum
+    want[0, :2] = [0.75, 0.25]                                     # bin 0 also takes its own weight clamped from bin -1
+    want[N - 1, N - 2:] = [1.0 / 3.0, 2.0 / 3.0]                   # bin N does not exist: [1/2, 1] over its sum
+    assert np.array_equal(m, want)
+    assert np.max(np.abs(m - np.eye(N))) == 0.5
+
+
+def test_vtln_refusals(engine):
+    from distant_speech_recognition_amd import _lib
+    with pytest.raises(_lib.BtkError) as e:
+        engine.fe_vtln_table(33, 1.0, 1.0, 3)
+    assert e.value.code == _lib.BTK_ERR_PARAMETER
+    with pytest.raises(_lib.BtkError) as e:
+        engine.fe_vtln_table(33, 1.0, 1.0, 2, inN=40)
+    assert e.value.code == _lib.BTK_ERR_DIMENSION
+
+
+@pytest.mark.parametrize("shape", [(13, 30), (13, 129)])
+@pytest.mark.parametrize("type", [0, 1, 2])
+def test_dct_table_bit_equal(engine, type, shape):
+    t = engine.fe_dct_table(type, *shape)
+    assert t.coef.dtype == np.float32 and np.array_equal(t.coef.reshape(shape), cf.dct_table(type, *shape))
+
+
+def test_dct_table_type1_is_scipy_dct2_and_unknown_type_refused(engine):
+    scipy_fft = pytest.importorskip("scipy.fft")
+    from distant_speech_recognition_amd import _lib
+    cepN, n = 13, 30
+    m = engine.fe_dct_table(1, cepN, n).matrix()
+    x = np.random.default_rng(0).normal(size=n)
+    assert np.max(np.abs(m @ x - 0.5 * scipy_fft.dct(x, type=2)[:cepN])) < 1e-5 * np.abs(x).sum()
+    with pytest.raises(_lib.BtkError) as e:
+        engine.fe_dct_table(3, cepN, n)
+    assert e.value.code == _lib.BTK_ERR_PARAMETER
+
+
+@pytest.mark.parametrize("pad", [True, False])
+def test_fe_frames_is_sample_features_count(engine, pad):
+    from distant_speech_recognition_amd.btk20 import feature
+    for n, D, shift in ((3000, 400, 160), (3000, 160, 160), (401, 400, 160), (400, 400, 160), (1000, 256, 100), (5, 256, 100)):
+        sf = feature.SampleFeaturePtr(block_len=D, shift_len=shift, pad_zeros=pad)
+        sf.set_samples(np.arange(n, dtype=np.float32) % 7 + 1)
+        count = 0
+        try:
+            while True:
+                sf.next()
+                count += 1
+        except StopIteration:
+            pass
+        assert engine.fe_frames(n, D, shift, pad) == count, (n, D, shift, pad, count)
+
+
+def test_process_refuses_before_it_touches_a_device():
+    """Every range check of btk_fe_process comes before its first device call: the refusals need no GPU."""
+    import ctypes
+    from distant_speech_recognition_amd import _lib
+    host = np.zeros(16, np.float32)                   # never read: the entry returns before anything is launched
+
+    def call(in_stage=0, want=(1, 2), D=160, shift=160, L=256, powN=129, in_dim=0, window=1):
+        q = _lib.FeParams()
+        q.S, q.C, q.T, q.in_stage, q.in_dim, q.len, q.pcm_stride = 1, 1, 4, in_stage, in_dim, 2000, 2000
+        q.D, q.shift, q.L, q.window, q.powN = D, shift, L, window, powN
+        for s in want:
+            q.out[s] = host.ctypes.data
+        return _lib.lib().btk_fe_process(ctypes.cast(ctypes.pointer(q), ctypes.c_void_p), host.ctypes.data_as(ctypes.c_void_p), None)
+
+    for kw in (dict(L=128), dict(L=300), dict(L=32768), dict(D=300, shift=100), dict(D=1, shift=1), dict(shift=161), dict(shift=0),
+               dict(powN=100), dict(powN=128), dict(in_stage=2, want=(5,), in_dim=0)):
+        assert call(**kw) == _lib.BTK_ERR_DIMENSION, kw
+    for kw in (dict(in_stage=6), dict(in_stage=-1), dict(want=()), dict(in_stage=2, want=(1, 2), in_dim=17), dict(window=2),
+               dict(want=(6,))):                      # unknown stage, nothing requested after the input stage, cepstra without a table
+        assert call(**kw) == _lib.BTK_ERR_PARAMETER, kw
+    assert b"btk_fe_process" in _lib.lib().btk_last_error()
+
+
+def test_fe_params_mirror_the_header():
+    """_lib.FeParams has the fields of btk_fe_params in the header's order."""
+    import os
+    import re
+    from distant_speech_recognition_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    txt = open(os.path.join(root, "include", "btkhip.h")).read()
+    body = re.search(r"typedef struct btk_fe_params \{(.*?)\} btk_fe_params;", txt, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            first, *rest = decl.split(",")
+            names += [re.sub(r"\[\d+\]", "", first.split()[-1]).lstrip("*")] + [r.strip().lstrip("*") for r in rest]
+    assert names == [f[0] for f in _lib.FeParams._fields_]
+
+
+def test_host_nodes_preemphasis_and_storage(tmp_path):
+    """PreemphasisFeature and StorageFeature are host nodes: the reference's arithmetic and frame rules without a device."""
+    from btk20.feature import SampleFeaturePtr, PreemphasisFeaturePtr, StorageFeaturePtr
+    from distant_speech_recognition_amd.btk20cpp import jindex_error
+    x = np.round(np.random.default_rng(1).normal(scale=3000.0, size=1000)).astype(np.float32)
+    s = SampleFeaturePtr(block_len=256, shift_len=100, pad_zeros=True)
+    s.set_samples(x)
+    pre = PreemphasisFeaturePtr(s, mu=0.95)
+    st = StorageFeaturePtr(pre)
+    got = np.stack([np.array(v) for v in st])
+    assert got.shape == (10, 256) and np.array_equal(got, cf.frames(x, 256, 100, 10, 0.95, 0.0, window=False))
+    assert np.array_equal(np.array(st.next(4)), got[4]) and st.frame_no() == 9
+    path = str(tmp_path / "frames.bin")
+    st.write(path)
+    st2 = StorageFeaturePtr(PreemphasisFeaturePtr(SampleFeaturePtr(block_len=256, shift_len=100, pad_zeros=True)))
+    st2.read(fileName=path)
+    assert st2.frame_no() == 9 and np.array_equal(np.array(st2.next(9)), got[9])
+    s.set_samples(x)
+    pre.reset()
+    a = pre.next()
+    assert np.shares_memory(a, pre.next(0))
+    with pytest.raises(jindex_error):
+        pre.next(5)
+    pre.next_speaker()

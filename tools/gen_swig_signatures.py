@@ -14,7 +14,8 @@ import sys
 REF = "/root/reference/btk20_src"
 FILES = ["feature/feature.i", "modulated/modulated.i", "beamformer/beamformer.i", "postfilter/postfilter.i",
          "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i"]
-CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
+CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
+           "LogFeature", "CepstralFeature", "StorageFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
            "SubbandBeamformer", "SubbandDS", "SubbandGSC", "SubbandGSCRLS", "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter",
            "McCowanPostFilter", "LefkimmiatisPostFilter", "MultiChannelWPEDereverberation", "MultiChannelWPEDereverberationFeature",
            "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream",
