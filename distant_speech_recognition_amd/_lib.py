@@ -160,6 +160,11 @@ SIGNATURES = {
     "btk_fe_mel_table": (_i, [_i, _f, _f, _f, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "btk_fe_vtln_table": (_i, [_i, _i, _d, _d, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "btk_fe_dct_table": (_i, [_i, _i, _i, _vp]),
+    # FFT block convolution: OverlapAdd::next / OverlapSave::next (convolution/convolution.cc:83-131, :196-230)
+    "btk_conv_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "btk_conv_filter_spectra": (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
+    "btk_conv_apply": (_i, [_vp, _l, _l, _l, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _l, _vp]),
+    "btk_conv_blocks": (_i, [_vp, _l, _l, _i, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

@@ -151,6 +151,7 @@ HammingFeature, FFTFeature = _mod.HammingFeaturePtr, _mod.FFTFeaturePtr
 PreemphasisFeature, SpectralPowerFeature, VTLNFeature = _mod.PreemphasisFeaturePtr, _mod.SpectralPowerFeaturePtr, _mod.VTLNFeaturePtr
 MelFeature, LogFeature, CepstralFeature = _mod.MelFeaturePtr, _mod.LogFeaturePtr, _mod.CepstralFeaturePtr
 StorageFeature = _mod.StorageFeaturePtr
+OverlapAdd, OverlapSave = _mod.OverlapAddPtr, _mod.OverlapSavePtr
 OverSampledDFTAnalysisBank, OverSampledDFTSynthesisBank = _mod.OverSampledDFTAnalysisBankPtr, _mod.OverSampledDFTSynthesisBankPtr
 SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _mod.SubbandGSCRLSPtr
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
@@ -166,4 +167,4 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
             "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
             "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
-            "LogFeature", "CepstralFeature", "StorageFeature"]
+            "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave"]

@@ -46,9 +46,13 @@ CLASS_METHOD_KWARGS = {
 }
 
 CTOR_KWARGS = {
+    'OverlapAddPtr': [('samp', None), ('impulse_response', None), ('fft_len', 0), ('nm', 'Overlap Add')],
+    'OverlapSavePtr': [('samp', None), ('impulse_response', None), ('nm', 'Overlap Save')],
     'LefkimmiatisPostFilterPtr': [('output', None), ('fftlen', None), ('min_sv', 1e-08), ('fbin_no1', 0), ('alpha', 0.6), ('type', 2), ('min_frames', 0), ('threshold', 0.99), ('nm', 'LefkimmiatisPostFilterPtr')],
     'PyVectorComplexFeatureStreamPtr': [('obj', None), ('name', 'PyVectorComplexFeatureStream')],
     'PyVectorFloatFeatureStreamPtr': [('obj', None), ('name', 'PyVectorFloatFeatureStream')],
+    # unit_test/correlate.py still spells the sample source's keywords the legacy way
+    'SampleFeaturePtr': [('fn', ''), ('blockLen', 320), ('shiftLen', 160), ('padZeros', False), ('nm', 'Sample')],
     'SnapShotArrayPtr': [('fftlen', None), ('chan_num', None)],
 }
 

@@ -1851,3 +1851,87 @@ def fe_process(x, in_stage="pcm", want=("cep",), D=None, shift=None, L=None, T=N
         q.out[s] = t.data_ptr()
     check(_lib.lib().btk_fe_process(C.cast(C.pointer(q), C.c_void_p), _ptr(x), _stream()))
     return out
+
+
+# ---- FFT block convolution (btk_conv_*): OverlapAdd::next / OverlapSave::next (convolution/convolution.cc:83-131, :196-230) ------
+def conv_plan(P, n_max=16384):
+    """(N, Lk, Bp, Q) that btk_conv_plan picks for P taps: transform length, outputs per tile, taps per partition, partitions."""
+    N, Lk, Bp, Q = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    check(_lib.lib().btk_conv_plan(int(P), int(n_max), C.byref(N), C.byref(Lk), C.byref(Bp), C.byref(Q)))
+    return N.value, Lk.value, Bp.value, Q.value
+
+
+class ConvFilter:
+    """Impulse responses as the half spectra btk_conv_apply multiplies with, and the plan they were cut by.
+    H complex64 [S_h][C][Q][N/2+1] on the device of h; S_h = 1 for filters shared by every stream."""
+
+    def __init__(self, H, P, N, Lk, Bp, Q):
+        self.H, self.P, self.N, self.Lk, self.Bp, self.Q = H, int(P), int(N), int(Lk), int(Bp), int(Q)
+        self.S_h, self.C = int(H.shape[0]), int(H.shape[1])
+
+
+def conv_filter(h, n_max=16384, plan=None):
+    """h float32 cuda [C][P] (shared by every stream) or [S][C][P] -> ConvFilter.  Taps given as float64 are rounded to float32
+    first.  plan: (N, Lk, Bp, Q) instead of conv_plan(P, n_max)'s, e.g. a tile length that divides a block length."""
+    if h.dim() == 2:
+        h = h.unsqueeze(0)
+    if h.dtype == torch.float64:
+        h = h.to(torch.float32)
+    h = h.contiguous()
+    _check(h, "h", torch.float32, 3)
+    S_h, Cn, P = h.shape
+    N, Lk, Bp, Q = conv_plan(P, n_max) if plan is None else (int(v) for v in plan)
+    H = torch.empty((S_h, Cn, max(Q, 1), max(N, 0) // 2 + 1), dtype=torch.complex64, device=h.device)
+    check(_lib.lib().btk_conv_filter_spectra(_ptr(h), P, S_h * Cn, P, N, Bp, Q, _ptr(H), _stream()))
+    return ConvFilter(H, P, N, Lk, Bp, Q)
+
+
+def _conv_rows(x, name):
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: x must be a float32 cuda tensor [S][samples] with contiguous rows" % name)
+    S, n = x.shape
+    stride = x.stride(0) if S > 1 else max(n, 1)
+    if stride < n:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: rows of x overlap" % name)
+    return x, S, n, stride
+
+
+def fir_convolve(x, filt, out_len=None, hist=0, out=None):
+    """y[s][c][n] = sum_p h[c][p] x[s][hist + n - p]: every row of x float32 [S][hist + len] filtered with every impulse response
+    of filt -> float32 [S][C][out_len].  The first `hist` samples of a row are the stream's past (zeros stand in front of them),
+    so a call on x[:, a - hist:] with hist >= P - 1 continues a call that ended at sample a; where a is a multiple of filt.Lk
+    the bits are those of one call.  out_len: len (default, what OverlapAdd hands out) up to len + P - 1 and beyond (zeros)."""
+    x, S, n, stride = _conv_rows(x, "fir_convolve")
+    hist = int(hist)
+    if hist < 0 or hist > n:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fir_convolve: hist=%d outside the rows' %d samples" % (hist, n))
+    ln = n - hist
+    out_len = ln if out_len is None else int(out_len)
+    if filt.S_h not in (1, S):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "fir_convolve: filters of %d streams, x has %d" % (filt.S_h, S))
+    if out is None:
+        out = torch.empty((S, filt.C, max(out_len, 0)), dtype=torch.float32, device=x.device)
+    ys = _check(out, "out", torch.float32, (S, filt.C, out_len), rows=True)
+    check(_lib.lib().btk_conv_apply(C.c_void_p(x.data_ptr() + 4 * hist), ln, hist, stride, S, _ptr(filt.H), filt.S_h, filt.C,
+                                    filt.P, filt.N, filt.Lk, filt.Bp, filt.Q, _ptr(out), out_len, ys, _stream()))
+    return out
+
+
+def conv_blocks(x, filt, L, block_step):
+    """OverlapSave::next for every block: x float32 [S][len], block t = samples t block_step .. + L - 1 (every block that fits),
+    filt a ConvFilter cut for N = L with Q = 1 (conv_filter(h, plan=(L, L - P + 1, P, 1))) -> float32 [S][C][T][L - P],
+    y[..][t][j] = sum_p h[p] x[t block_step + j + P - p]."""
+    x, S, n, stride = _conv_rows(x, "conv_blocks")
+    L, block_step = int(L), int(block_step)
+    if filt.N != L or filt.Q != 1:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "conv_blocks: the filter was cut for N=%d, Q=%d, not for blocks of %d"
+                            % (filt.N, filt.Q, L))
+    if filt.S_h not in (1, S):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "conv_blocks: filters of %d streams, x has %d" % (filt.S_h, S))
+    T = (n - L) // block_step + 1 if (block_step > 0 and n >= L) else 0
+    out = torch.empty((S, filt.C, max(T, 0), max(L - filt.P, 0)), dtype=torch.float32, device=x.device)
+    check(_lib.lib().btk_conv_blocks(_ptr(x), n, stride, S, T, block_step, _ptr(filt.H), filt.S_h, filt.C, filt.P, L, _ptr(out),
+                                     _stream()))
+    return out

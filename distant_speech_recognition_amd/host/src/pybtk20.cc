@@ -1,6 +1,6 @@
 // pybtk20.cc -- Python binding of the C++ node layer (libbtk20hip.so): the classes the reference exposes through SWIG
 // (stream/stream.i, feature/feature.i, modulated/modulated.i, beamformer/beamformer.i, postfilter/postfilter.i,
-// dereverberation/dereverberation.i) bound with pybind11 under the same names.
+// dereverberation/dereverberation.i, convolution/convolution.i) bound with pybind11 under the same names.
 //   * a bound object IS the C++ node: the holder shares Countable's intrusive count with the refcountable_ptrs the nodes keep
 //     of each other, so Python and C++ references are one population;
 //   * next() returns a numpy VIEW of the node's vector_ (no copy; the array keeps the node alive) -- the reference's typemap
@@ -19,6 +19,7 @@
 #include "beamformer/beamformer.h"
 #include "dereverberation/dereverberation.h"
 #include "aec/aec.h"
+#include "convolution/convolution.h"
 #include "feature/feature.h"
 #include "modulated/modulated.h"
 #include "postfilter/postfilter.h"
@@ -437,6 +438,33 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("set_block_frames", [](CepstralFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
       .def("block_frames", [](CepstralFeature& f) { return f.block_frames(); })
       .def("launches", [](CepstralFeature& f) { return f.launches(); });
+
+  // ---- convolution/convolution.h (convolution/convolution.i:45-107); block_frames / set_block_frames / launches / plan are the engine's additions
+  py::class_<OverlapAdd, VectorFloatFeatureStream, cref<OverlapAdd>>(m, "OverlapAddPtr")
+      .def(py::init([](py::object samp, py::array_t<double, py::array::c_style | py::array::forcecast> impulse_response, unsigned fft_len,
+                       const std::string& nm, long block_frames) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             GslVec h(impulse_response);
+             return new OverlapAdd(sp, h.v, fft_len, nm, block_frames);
+           }), py::arg("samp"), py::arg("impulse_response"), py::arg("fft_len") = 0, py::arg("nm") = "Overlap Add", py::arg("block_frames") = 0)
+      .def("fftLen", &OverlapAdd::fftLen)
+      .def("taps", [](OverlapAdd& f) { return f.taps(); })
+      .def("plan", [](OverlapAdd& f) { int N, Lk, Bp, Q; f.plan(&N, &Lk, &Bp, &Q); return py::make_tuple(N, Lk, Bp, Q); })
+      .def("set_block_frames", [](OverlapAdd& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](OverlapAdd& f) { return f.block_frames(); })
+      .def("launches", [](OverlapAdd& f) { return f.launches(); });
+  py::class_<OverlapSave, VectorFloatFeatureStream, cref<OverlapSave>>(m, "OverlapSavePtr")
+      .def(py::init([](py::object samp, py::array_t<double, py::array::c_style | py::array::forcecast> impulse_response, const std::string& nm,
+                       long block_frames) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             GslVec h(impulse_response);
+             return new OverlapSave(sp, h.v, nm, block_frames);
+           }), py::arg("samp"), py::arg("impulse_response"), py::arg("nm") = "Overlap Save", py::arg("block_frames") = 0)
+      .def("taps", [](OverlapSave& f) { return f.taps(); })
+      .def("plan", [](OverlapSave& f) { int N, Lk, Bp, Q; f.plan(&N, &Lk, &Bp, &Q); return py::make_tuple(N, Lk, Bp, Q); })
+      .def("set_block_frames", [](OverlapSave& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](OverlapSave& f) { return f.block_frames(); })
+      .def("launches", [](OverlapSave& f) { return f.launches(); });
 
   // ---- modulated/modulated.h
   py::class_<OverSampledDFTAnalysisBank, VectorComplexFeatureStream, cref<OverSampledDFTAnalysisBank>>(m, "OverSampledDFTAnalysisBankPtr")

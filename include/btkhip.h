@@ -731,6 +731,42 @@ int  btk_fe_vtln_table(int N, int inN, double ratio, double edge, int version, i
  * BTK_ERR_PARAMETER for another type, BTK_ERR_DIMENSION for cepN, filterN < 1 (type 0: filterN < 2).                           */
 int  btk_fe_dct_table(int type, int cepN, int filterN, float* dct);
 
+/* ---- FFT block convolution: OverlapAdd::next / OverlapSave::next (convolution/convolution.cc:83-131, :196-230) ----------------
+ * FIR filtering of whole rows by N-point real transforms (fft_long.h, N a power of two from 256 to 16384), one workgroup per
+ * (output row, tile) in the overlap-save arrangement: a span of N samples, forward transform, product with the filter's half
+ * spectrum (bins 0 and N/2 real times real, convolution.cc:103-104), inverse transform, Lk samples kept.  P taps are cut into Q
+ * partitions of Bp taps (the last may be shorter), Lk + Bp - 1 <= N; a tile costs Q + 1 transforms.  OverlapAdd's float32
+ * running sum (convolution.cc:116-127) is not re-enacted: the result is the same linear convolution.
+ *
+ * Host code, no device: the rule that picks transform, tile and partition for P taps, with N capped by n_max (a power of two
+ * from 256 to 16384):  N = min(max(next_pow2(4 P), 8192), n_max);  Bp = P, Q = 1 if P <= N/2 + 1, else Bp = N/2,
+ * Q = ceil(P / Bp);  Lk = N - Bp + 1.  (8192 is the length that filtered long rows fastest for short filters; a caller with
+ * short rows caps N with n_max.)  BTK_ERR_DIMENSION for P < 1 or a bad n_max, BTK_ERR_PARAMETER for a null pointer.                          */
+int  btk_conv_plan(int P, int n_max, int* N, int* Lk, int* Bp, int* Q);
+/* The filters' half spectra (OverlapAdd::set_impulse_response_, convolution.cc:43-60, in float32 on the device):
+ *   h [dev] float32 [R] rows of P taps, h_stride apart  ->  H [dev] complex64 [R][Q][N/2+1], partition q = taps q Bp ..
+ * BTK_ERR_DIMENSION for N no power of two in 256 .. 16384, P < 1, Q Bp < P, (Q - 1) Bp >= P, h_stride < P, R < 1.             */
+int  btk_conv_filter_spectra(const float* h, long h_stride, int R, int P, int N, int Bp, int Q, void* H, void* stream);
+/* y[s][c][n] = sum_{p < P} h[s or 0][c][p] x[s][n - p],  0 <= n < out_len  (out_len = len: what OverlapAdd hands out,
+ * convolution.cc:120-121; len + P - 1: the whole convolution):
+ *   x [dev] float32: S row pointers x + s x_stride, each with `len` samples at 0 .. len - 1 and `hist` samples of the stream's
+ *     past at -hist .. -1; samples before -hist and from len on are zero and that memory is never read (a second call whose
+ *     hist covers P - 1 samples continues the stream of the first)
+ *   H [dev] complex64 [S_h][C][Q][N/2+1] from btk_conv_filter_spectra, S_h = 1 (shared) or S
+ *   y [dev] float32 [S][C] rows of out_len samples, y_stride apart
+ * Tile j holds outputs j Lk ..; a span element no stored output depends on is read as zero, so calls that cut a row at multiples
+ * of Lk give the bits of one call.  BTK_ERR_DIMENSION for a bad N, P, Bp, Q (as above), Lk + Bp - 1 > N, S_h not 1 or S,
+ * negative lengths, out_len < 1 or strides shorter than the rows; BTK_ERR_PARAMETER for null pointers; nothing is launched.   */
+int  btk_conv_apply(const float* x, long len, long hist, long x_stride, int S, const void* H, int S_h, int C, int P, int N, int Lk,
+                    int Bp, int Q, float* y, long out_len, long y_stride, void* stream);
+/* OverlapSave::next (convolution.cc:196-230) for T stand-alone blocks of L samples, block t at samples t block_step .. of each
+ * row (zero from len on): an L-point circular convolution with H [S_h][C][1][L/2+1] (Q = 1, Bp = P, N = L) of which samples
+ * P .. L - 1 are kept (:225-226; index P - 1 is dropped as there):  y [dev] float32 [S][C][T][L - P],
+ *   y[..][t][j] = sum_{p < P} h[p] x[t block_step + j + P - p].
+ * BTK_ERR_DIMENSION for L no power of two in 256 .. 16384, P < 1, P >= L (:180-181), S_h not 1 or S, T < 1, block_step < 1.   */
+int  btk_conv_blocks(const float* x, long len, long x_stride, int S, long T, long block_step, const void* H, int S_h, int C, int P,
+                     int L, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,14 +13,14 @@ import sys
 
 REF = "/root/reference/btk20_src"
 FILES = ["feature/feature.i", "modulated/modulated.i", "beamformer/beamformer.i", "postfilter/postfilter.i",
-         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i"]
+         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i", "convolution/convolution.i"]
 CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
            "LogFeature", "CepstralFeature", "StorageFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
            "SubbandBeamformer", "SubbandDS", "SubbandGSC", "SubbandGSCRLS", "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter",
            "McCowanPostFilter", "LefkimmiatisPostFilter", "MultiChannelWPEDereverberation", "MultiChannelWPEDereverberationFeature",
            "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream",
            "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature", "BlockKalmanFilterEchoCancellationFeature",
-           "DTDBlockKalmanFilterEchoCancellationFeature"]
+           "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
 
 
