@@ -90,6 +90,7 @@ SIGNATURES = {
     "btk_gather_rows": (_i, [_vp, _vp, _i, _l, _vp]),
     "btk_cov_frame_gate": (_i, [_vp, _vp, _i, _l, _l, _f, _vp, _vp, _vp]),
     "btk_cov_accumulate": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _i, _vp]),
+    "btk_cov_scale": (_i, [_vp, _d, _i, _i, _i, _vp]),
     "btk_cov_finalize": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "btk_cov_mask_count": (_i, [_vp, _vp, _i, _i, _l, _l, _vp, _vp]),
     "btk_cov_trace_normalize": (_i, [_vp, _i, _i, _vp]),

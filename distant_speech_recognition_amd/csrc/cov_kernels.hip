@@ -18,6 +18,7 @@
 // optional.  R [S][K][N][N] complex64 row-major, accumulated in place (+=).  A frame whose weight
 // is 0 contributes nothing in any kernel, even if its snapshot is NaN or Inf: the reference skips
 // it (pybeamformer.py:1080, :1137-1147).
+#include <algorithm>
 #include "btk_internal.h"
 
 namespace {
@@ -371,9 +372,28 @@ void cov_finalize_kernel(float2* __restrict__ R, const float* __restrict__ count
   }
 }
 
+// R <- a R, the product formed in double and rounded once.  A recursion R <- a R + sum_t w_t x x^H that is carried from block to
+// block on the device (the post-filters' spectral densities) then takes the roundings of its host form float(a * double(R)) + sum.
+__global__ __launch_bounds__(256)
+void cov_scale_kernel(float* __restrict__ R, double a, long n)
+{
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += 256L * gridDim.x) R[i] = (float)(a * (double)R[i]);
+}
+
 }  // namespace
 
 extern "C" {
+
+int btk_cov_scale(void* R, double a, int S, int K, int N, void* stream)
+{
+  if (!R) return btk_set_error(BTK_ERR_PARAMETER, "btk_cov_scale: null argument");
+  if (S <= 0 || K <= 0 || N <= 0) return btk_set_error(BTK_ERR_DIMENSION, "btk_cov_scale: bad sizes S=%d K=%d N=%d", S, K, N);
+  const long n = 2L * S * K * N * N;                     // floats of complex64 [S][K][N][N]
+  const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(cov_scale_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), static_cast<float*>(R), a, n);
+  BTK_HIP_CHECK(hipGetLastError());
+  return BTK_OK;
+}
 
 int btk_cov_accumulate(const void* X, const float* tf_weights, const float* frame_weights, void* R,
                        int S, int K, int N, long T_stride, long T, int use_mfma, void* stream)

@@ -1022,6 +1022,15 @@ def cov_accumulate(X, R=None, tf_weights=None, frame_weights=None, use_mfma=True
     return R
 
 
+def cov_scale(R, a):
+    """R <- float32(a * float64(R)) in place: the decay step of a recursion R <- a R + sum_t w x x^H kept on the device."""
+    _check(R, "R", torch.complex64, 4)
+    S, K, N, _ = R.shape
+    _check(R, "R", torch.complex64, (S, K, N, N))
+    check(_lib.lib().btk_cov_scale(_ptr(R), float(a), S, K, N, _stream()))
+    return R
+
+
 def cov_finalize(R, count, gamma=0.0):
     S, K, N, _ = R.shape
     per_bin = int(count.dim() == 2)

@@ -6,6 +6,7 @@
 #include <functional>
 #include <list>
 #include <memory>
+#include <string>
 #include <vector>
 #include "stream/stream.h"
 #include "modulated/modulated.h"
@@ -168,8 +169,11 @@ class SubbandBeamformer : public VectorComplexFeatureStream {
   bool i16_stream_possible();
   void begin_i16_stream();
   bool i16_stream() const { return pcm_i16_; }
+  void check_i16_sources();                              // a 16-bit stream: every bank's check_i16_source()
  protected:
-  bool load_chunk_();
+  bool load_chunk_();                                    // an error under a 16-bit stream is latched: every later call raises it again, until reset()
+  bool load_chunk_unlatched_();
+  std::string stream_error_;
   void pull_bank_(size_t c);
   void pull_banks_(size_t c0, size_t c1);
   void plan_from_pulled_(BlockPlan& p, size_t nbanks) const;
@@ -513,7 +517,11 @@ class SubbandGraphPool : public Countable {
   unsigned size() const { return (unsigned)graphs_.size(); }
   bool next();                                              // one more output block of every graph that has one; false: all have ended
   const gsl_vector_float* output(unsigned g) const;         // graph g's block of the last next(); NULL once that graph has ended
+  // graph g has handed out its last block.  Never true while a later next() / next_round() still delivers a block of g (what a
+  // round staged ahead knows about a graph's end takes effect when that round becomes the current one); stays true until reset().
   bool is_end(unsigned g) const;
+  // An error inside next() / next_round() (a source whose samples changed under a 16-bit stream, graphs out of lock step) is
+  // latched: no block is handed out any more and every later call raises it again, until reset().
   // The blocks the next calls of next() would hand out, a ROUND at a time: next_round() makes the blocks every graph still has in
   // the resident round (a new round when none has any) available at once -- false: all graphs have ended -- and round_blocks(g, &p)
   // says how many graph g got (0: that graph has ended or had no block in this round) and where they lie (n x shiftlen floats,
@@ -533,6 +541,8 @@ class SubbandGraphPool : public Countable {
     long round_first, round_n;   // next_round(): the blocks of the current round handed out at once
   };
   bool load_round_();
+  bool load_round_unlatched_();
+  std::string error_;             // the latched error of load_round_ (empty: none)
   // one round's input on its way to the device: every live graph's block plan and its sample windows in one block [G][N][Lmax]
   struct Stage {
     std::vector<SubbandBeamformer::BlockPlan> plans;

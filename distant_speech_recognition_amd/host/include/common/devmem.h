@@ -18,6 +18,12 @@ void btk_node_synchronize();
 // allocations the node layer has made so far in this process: {hipMalloc, hipHostMalloc} (tests and the bench use the
 // difference across blocks to show that a steady-state block allocates nothing)
 void btk_node_alloc_counts(long* device_allocs, long* pinned_allocs);
+// bytes the node layer has copied from the device to the host in this process since the last reset.  Every device-to-host copy
+// of a node reports its size with btk_node_count_d2h() (one relaxed atomic add): a graph that ends in a synthesis bank brings
+// nothing but its PCM back, and the difference across rounds shows it (tests/test_gpu_node_midstream.py)
+long long btk_node_d2h_bytes();
+void btk_node_d2h_bytes_reset();
+void btk_node_count_d2h(size_t bytes);
 
 // where a block's host time goes, summed over the process since the last reset (host/examples/node_api_bench.cc, bench.py
 // stages.node_api): pull = the analysis banks drawing their input blocks from the source nodes into the pinned windows;

@@ -59,6 +59,7 @@ class SampleFeature : public VectorFloatFeatureStream {
   unsigned shiftlen() const { return shiftLen_; }
   // counts the changes of the samples (a reader that keeps the pcm16() pointer compares it before every use)
   unsigned long samples_generation() const { return samples_gen_; }
+  size_t position() const { return cur_; }                   // sample index the next block starts at
  private:
   SampleFeature(const SampleFeature&);
   SampleFeature& operator=(const SampleFeature&);
@@ -74,7 +75,7 @@ class SampleFeature : public VectorFloatFeatureStream {
   PinnedBuffer pcm16_;           // int16 shadow of samples_ (pcm16())
   int pcm16_state_;              // 0: not built for the current samples, 1: valid, -1: the samples are not 16-bit PCM
   unsigned long samples_gen_;
-  void samples_changed_() { pcm16_state_ = 0; samples_gen_++; }
+  void samples_changed_();       // waits for uploads that still read the int16 shadow before it may be rebuilt
 };
 
 // HammingFeature (reference feature/feature.h:492-507, feature/feature.cc:1177-1200): the float64 window times the source's

@@ -70,6 +70,9 @@ class OverSampledDFTAnalysisBank : public VectorComplexFeatureStream {
   bool i16_source_ok() const;                           // ... and nothing has been pulled yet
   void begin_i16();
   bool i16_mode() const { return src16_ != NULL; }
+  // 16-bit mode: the source still holds the samples begin_i16() saw and stands where this bank left it; jconsistency_error
+  // otherwise.  A node that planned a block ahead asks before it makes that block the current one.
+  void check_i16_source() const;
   const short* window16(long b0) const { return src16_ + src16_pos0_ + (size_t)b0 * D_; }
   const btk_fb_t* plan() const { return plan_; }
   unsigned delay_compensation_type() const { return dct_; }

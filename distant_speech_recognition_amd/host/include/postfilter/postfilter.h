@@ -37,6 +37,7 @@ class ZelinskiPostFilter : public VectorComplexFeatureStream, public BlockSource
   virtual void compute_(long from_frame);
   bool advance_chunk_();                    // the beamformer's next block of snapshots; the recursions continue from this one's end
   void csd_state_(long t, std::vector<float>& R);
+  void csd_advance_();                      // the CSD state after the current block's last frame, on the device
   const float* host_output_();              // the filtered block mirrored on the host (fetched on demand)
   const gsl_vector_complex* next_manual_(int frame_no);
   // the reference keeps the N x N spectral densities of every bin in BeamformerWeights::CSDs(); this engine keeps only their
@@ -67,7 +68,9 @@ class ZelinskiPostFilter : public VectorComplexFeatureStream, public BlockSource
   long manual_frames_;
   long base_;                               // stream index of the current block's first frame
   bool carry_state_;                        // the next compute_() continues the recursions (a new block of the same stream)
-  std::vector<float> csd_carry_;            // CSD state after the block before, complex64 [K][N][N] (for CSDs())
+  DeviceBuffer dCsd_, dCsdW_;               // CSD state after the block before, complex64 [K][N][N] (for CSDs()); frame weights of a block
+  size_t csd_dev_n_;                        // floats of dCsd_ that hold such a state (0: none)
+  std::vector<float> csd_carry_;            // host copy of dCsd_, fetched when CSDs() is asked for (empty until then)
   long handed_;                             // block protocol mark (see SubbandDS::advance_to)
 };
 typedef Inherit<ZelinskiPostFilter, VectorComplexFeatureStreamPtr> ZelinskiPostFilterPtr;

@@ -42,6 +42,7 @@ void d2h(void* h, const void* d, size_t n)
 {
   if (!n) return;
   check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
+  btk_node_count_d2h(n);
   btk_node_synchronize();
 }
 long even_pitch(long frames) { return frames + (frames & 1); }

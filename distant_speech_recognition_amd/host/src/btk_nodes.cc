@@ -129,6 +129,7 @@ class PullPool {
 };
 
 std::atomic<long> g_device_allocs(0), g_pinned_allocs(0);
+std::atomic<long long> g_d2h_bytes(0);
 std::atomic<long long> g_pull_ns(0), g_upload_ns(0), g_device_ns(0);
 struct ScopedNs {                                   // adds the scope's wall time to one of the counters of btk_node_timers()
   std::atomic<long long>& acc;
@@ -139,12 +140,14 @@ struct ScopedNs {                                   // adds the scope's wall tim
 
 hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
 // a host thread's second stream: uploads of the block AFTER the current one (16-bit streams, SubbandBeamformer::prefetch_next_)
+thread_local hipStream_t t_cstream = NULL;
 hipStream_t cstream()
 {
-  static thread_local hipStream_t st = NULL;
-  if (!st) check_hip(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-  return st;
+  if (!t_cstream) check_hip(hipStreamCreateWithFlags(&t_cstream, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+  return t_cstream;
 }
+// waits for the copies staged ahead, if this thread ever staged any (a host without a device never opens the stream)
+void csync_if_open() { if (t_cstream) (void)hipStreamSynchronize(t_cstream); }
 void nsync() { check_hip(hipStreamSynchronize(nstream()), "hipStreamSynchronize"); }
 
 // one-off device blocks of the design-time paths (weight design, WPE estimate, CSD rebuild): not the per-block steady state
@@ -167,6 +170,7 @@ void d2h(void* h, const void* d, size_t n)
 {
   if (!n) return;
   check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
+  btk_node_count_d2h(n);
   nsync();
 }
 // the asynchronous forms: `h` is pinned memory that stays untouched until the stream has passed the copy
@@ -176,7 +180,9 @@ void h2d_async(void* d, const void* h, size_t n)
 }
 void d2h_async(void* h, const void* d, size_t n)
 {
-  if (n) check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
+  if (!n) return;
+  check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
+  btk_node_count_d2h(n);
 }
 void d2d_async(void* dst, const void* src, size_t n)
 {
@@ -267,6 +273,10 @@ void btk_node_alloc_counts(long* device_allocs, long* pinned_allocs)
   if (device_allocs) *device_allocs = g_device_allocs.load();
   if (pinned_allocs) *pinned_allocs = g_pinned_allocs.load();
 }
+
+long long btk_node_d2h_bytes() { return g_d2h_bytes.load(std::memory_order_relaxed); }
+void btk_node_d2h_bytes_reset() { g_d2h_bytes.store(0, std::memory_order_relaxed); }
+void btk_node_count_d2h(size_t bytes) { g_d2h_bytes.fetch_add((long long)bytes, std::memory_order_relaxed); }
 
 void btk_node_timers(double* pull_s, double* upload_s, double* device_s)
 {
@@ -412,6 +422,16 @@ void SampleFeature::set_samples(const float* samples, size_t n)
   is_end_ = false;
   samples_changed_();
   (void)pcm16();                       // load time, like read(): the 16-bit view of the utterance (a WAV is 16-bit PCM to begin with)
+}
+
+// Every change of the samples ends here.  An upload staged ahead by a 16-bit stream (SubbandBeamformer::prefetch_next_,
+// SubbandGraphPool::stage_round_) may still be reading the int16 copy on the thread's copy stream, and pcm16() rebuilds that copy
+// in place: wait for the stream first, so that no block goes up with samples of two utterances.
+void SampleFeature::samples_changed_()
+{
+  if (pcm16_.get()) csync_if_open();
+  pcm16_state_ = 0;
+  samples_gen_++;
 }
 
 static bool node_i16_enabled()                        // BTK_NODE_I16=0: no 16-bit views, no 16-bit streams (read whenever it matters)
@@ -714,6 +734,19 @@ void OverSampledDFTAnalysisBank::begin_i16()
   src16_gen_ = sf->samples_generation();
 }
 
+static void throw_i16_source_changed(const String& nm)
+{
+  throw jconsistency_error("OverSampledDFTAnalysisBank %s: the source was moved or its samples changed while the bank streamed "
+                           "them as 16-bit PCM; reset() the graph after changing an utterance\n", nm.c_str());
+}
+
+void OverSampledDFTAnalysisBank::check_i16_source() const
+{
+  if (!src16_) return;
+  SampleFeature* sf = dynamic_cast<SampleFeature*>(samp_.operator->());
+  if (!sf || sf->samples_generation() != src16_gen_ || sf->position() != src16_pos0_ + (size_t)nblk_ * D_) throw_i16_source_changed(name());
+}
+
 // one round of input: at most block_frames() blocks of D samples from the upstream node (modulated.cc:419-438 pulls one per frame)
 bool OverSampledDFTAnalysisBank::pull_more()
 {
@@ -727,9 +760,7 @@ bool OverSampledDFTAnalysisBank::pull_more()
       if (ask <= 0) break;
       size_t pos = 0;
       const long n = sf->advance_blocks(ask, &pos);
-      if (n > 0 && (pos != src16_pos0_ + (size_t)nblk_ * D_ || sf->samples_generation() != src16_gen_))
-        throw jconsistency_error("OverSampledDFTAnalysisBank %s: the source was moved or its samples changed while the bank streamed "
-                                 "them as 16-bit PCM; reset() the graph after changing an utterance\n", name().c_str());
+      if (n > 0 && (pos != src16_pos0_ + (size_t)nblk_ * D_ || sf->samples_generation() != src16_gen_)) throw_i16_source_changed(name());
       nblk_ += n; got += n;
       if (n < ask) { eos_ = true; break; }
     }
@@ -1426,6 +1457,7 @@ void SubbandBeamformer::free_device_()
   dX_ = NULL; dXfull_ = NULL; T_ = 0; Xhost_.clear();
   chunk_base_ = 0; chunk_loaded_ = false; channels_ended_ = false; pcm_valid_ = false; snap_valid_ = false; pcm_L_ = 0; pcm_t0_ = 0;
   pcm_i16_ = false; pcm_f32_valid_ = false; pcm_pitch_ = 0;
+  stream_error_.clear();
   if (pre_valid_) { (void)hipStreamSynchronize(cstream()); pre_valid_ = false; }     // copies of a block nobody will ask for
 }
 void SubbandBeamformer::set_channel(VectorComplexFeatureStreamPtr& chan) { channelList_.push_back(chan); }
@@ -1492,6 +1524,11 @@ bool SubbandBeamformer::i16_stream_possible()
   if (chunk_loaded_ || !node_i16_enabled() || !banks_only()) return false;
   for (size_t c = 0; c < banks_.size(); c++) if (!banks_[c]->i16_source_ok()) return false;
   return true;
+}
+
+void SubbandBeamformer::check_i16_sources()
+{
+  if (pcm_i16_) for (size_t c = 0; c < banks_.size(); c++) banks_[c]->check_i16_source();
 }
 
 void SubbandBeamformer::begin_i16_stream()
@@ -1613,6 +1650,21 @@ void SubbandBeamformer::prefetch_next_(const BlockPlan& cur)
 // Returns false when the channels have no further frame (the block is then empty).
 bool SubbandBeamformer::load_chunk_()
 {
+  if (!stream_error_.empty()) throw jconsistency_error("%s", stream_error_.c_str());
+  try {
+    return load_chunk_unlatched_();
+  } catch (jiterator_error&) {
+    throw;
+  } catch (j_error& e) {
+    // a 16-bit stream reads the utterance where its sources keep it and runs a block ahead of what it serves: after an error the
+    // node's state and the sources' no longer belong together, so nothing more comes out of this stream
+    if (pcm_i16_) stream_error_ = e.what();
+    throw;
+  }
+}
+
+bool SubbandBeamformer::load_chunk_unlatched_()
+{
   const unsigned N = chanN(), K = fftLen2_ + 1;
   if (N == 0) throw j_error("set channels first\n");
   if (banks_only()) {
@@ -1623,7 +1675,10 @@ bool SubbandBeamformer::load_chunk_()
     BlockPlan p, p0;
     char* dp = NULL;
     if (pre_valid_) {
-      // a 16-bit stream: this block was planned and sent on its way while the one before was computed and served (prefetch_next_)
+      // a 16-bit stream: this block was planned and sent on its way while the one before was computed and served (prefetch_next_).
+      // It becomes the current block only if the sources still are what they were then -- the check the pull of the block after it
+      // would make, made BEFORE anything is committed
+      check_i16_sources();
       ScopedNs timer(g_upload_ns);
       check_hip(hipStreamSynchronize(cstream()), "hipStreamSynchronize");      // (the host waits: a stream-side wait on an event made the copies slower)
       dPcm16Buf_.swap(dPcm16Next_);
@@ -2335,7 +2390,7 @@ ZelinskiPostFilter::ZelinskiPostFilter(VectorComplexFeatureStreamPtr& output, un
     : VectorComplexFeatureStream(fftLen, nm), fftLen_(fftLen), samp_(output), type_((PostfilterType)type), alpha_(alpha),
       min_frames_(minFrames), has_bf_ptr_(false), Yhost_valid_(false), T_(0), prepared_(false), bf_version_(0), dPhi_(NULL), dPsi_(NULL), dWl_(NULL),
       wp1_(gsl_vector_complex_calloc(fftLen)), hist_start_(0), own_weights_(NULL), manual_frames_(0), base_(0), carry_state_(false),
-      handed_(-1)
+      csd_dev_n_(0), handed_(-1)
 {
   if (output->size() != fftLen) throw jdimension_error("Input block length (%d) != fftLen (%d)\n", output->size(), fftLen);
 }
@@ -2379,28 +2434,41 @@ void ZelinskiPostFilter::bind_csd_provider_()
     bf_ptr_->beamformer_weight_object()->set_csd_provider([this](gsl_vector_complex** out) { fill_csds_(out); }, this);
 }
 
+// the frame weights of csd_state_ / csd_advance_ below: fw[tau - base] for the block's frames lo .. t (zero before); returns prod of a over them: what the state before the block keeps
+static double csd_frame_weights(long t, long lo, long base, double alpha, std::vector<float>& fw)
+{
+  double tail = 1.0;                                                  // prod of a_sigma over sigma in (tau, t]
+  for (long tau = t; tau >= lo; tau--) {
+    const double a_tau = (tau <= 1) ? 0.0 : alpha;
+    fw[(size_t)(tau - base)] = (float)((1.0 - a_tau) * tail);
+    tail *= a_tau;
+    if (tail == 0.0) break;
+  }
+  return tail;
+}
+
 // BeamformerWeights::CSDs() on demand (postfilter.cc:77-116): Phi_ij <- a Phi_ij + (1 - a) x'_i conj x'_j for i < j and the same
 // recursion on |x'_i|^2, x' = conj(d) x, a = 0 for the post-filter's first two frames, history restarted where the weights were
 // recomputed.  The recursion is linear, so the state after frame t of the current block is
 //   (prod of a over the block's frames up to t) * [state after the block before]  +  sum_tau fw[tau] x(tau) x(tau)^H,
 // fw[tau] = (1 - a_tau) prod_{sigma > tau} a_sigma: ONE weighted covariance launch (btk_cov_accumulate) over the block's raw
-// snapshots plus the carried matrices (csd_carry_, refreshed whenever a block is used up).  R: complex64 [K][N][N], unrotated.
+// snapshots plus the carried matrices.  Those stay on the device (dCsd_, csd_advance_ whenever a block is used up); csd_carry_ is
+// their host copy, fetched here when somebody asks.  R: complex64 [K][N][N], unrotated.
 void ZelinskiPostFilter::csd_state_(long t, std::vector<float>& R)
 {
   const unsigned K = fftLen_ / 2 + 1, N = bf_ptr_->chanN();
   R.assign((size_t)2 * K * N * N, 0.f);
+  if (csd_dev_n_ == R.size() && csd_carry_.empty()) {
+    csd_carry_.resize(R.size());
+    d2h(csd_carry_.data(), dCsd_.get(), sizeof(float) * R.size());
+  }
   const long lo = std::max(hist_start_, base_);                      // first frame of this block that belongs to the history
   if (t < lo && csd_carry_.empty()) return;
   const long Tn = t - base_ + 1;                                      // frames of the block up to t
-  double tail = 1.0;                                                  // prod of a_sigma over sigma in (tau, t]
+  double tail = 1.0;
   if (Tn > 0) {
     std::vector<float> fw((size_t)Tn, 0.f);
-    for (long tau = t; tau >= lo; tau--) {
-      const double a_tau = (tau <= 1) ? 0.0 : alpha_;
-      fw[(size_t)(tau - base_)] = (float)((1.0 - a_tau) * tail);
-      tail *= a_tau;
-      if (tail == 0.0) break;
-    }
+    tail = csd_frame_weights(t, lo, base_, alpha_, fw);
     void* dX = bf_ptr_->device_snapshots();
     const long Tstride = bf_ptr_->num_frames();
     void* dF = dev_alloc(sizeof(float) * Tn);
@@ -2414,6 +2482,27 @@ void ZelinskiPostFilter::csd_state_(long t, std::vector<float>& R)
   }
   if (hist_start_ < base_ && csd_carry_.size() == R.size() && tail != 0.0)
     for (size_t i = 0; i < R.size(); i++) R[i] += (float)(tail * csd_carry_[i]);
+}
+
+// The block is used up: the state after its last frame, formed where the snapshots lie -- the carried matrices decayed
+// (btk_cov_scale: the roundings of csd_state_'s host form), the block's weighted sum added (btk_cov_accumulate) -- so that a
+// post-filter under a synthesis bank brings nothing back to the host per block.
+void ZelinskiPostFilter::csd_advance_()
+{
+  const unsigned K = fftLen_ / 2 + 1, N = bf_ptr_->chanN();
+  const size_t n = (size_t)2 * K * N * N;
+  std::vector<float> fw((size_t)T_, 0.f);
+  const double tail = csd_frame_weights(base_ + T_ - 1, std::max(hist_start_, base_), base_, alpha_, fw);
+  void* dX = bf_ptr_->device_snapshots();
+  const bool keep = hist_start_ < base_ && csd_dev_n_ == n && tail != 0.0;
+  void* dC = dCsd_.ensure(sizeof(float) * n);
+  void* dF = dCsdW_.ensure(sizeof(float) * T_);
+  if (keep) check_abi(btk_cov_scale(dC, tail, 1, (int)K, (int)N, nstream()));
+  else dev_zero_async(dC, sizeof(float) * n);
+  h2d(dF, fw.data(), sizeof(float) * T_);
+  check_abi(btk_cov_accumulate(dX, NULL, (const float*)dF, dC, 1, (int)K, (int)N, bf_ptr_->num_frames(), T_, 0, nstream()));
+  csd_dev_n_ = n;
+  csd_carry_.clear();
 }
 
 void ZelinskiPostFilter::fill_csds_(gsl_vector_complex** out)
@@ -2561,7 +2650,7 @@ void ZelinskiPostFilter::compute_(long from_frame)
   }
   Yhost_valid_ = false;
   bf_version_ = bf->weights_version();
-  if (!carry) { hist_start_ = base_ + from_frame; csd_carry_.clear(); }
+  if (!carry) { hist_start_ = base_ + from_frame; csd_carry_.clear(); csd_dev_n_ = 0; }
   bind_csd_provider_();
   prepared_ = true;
 }
@@ -2573,11 +2662,7 @@ bool ZelinskiPostFilter::advance_chunk_()
   if (!has_bf_ptr_) return false;
   if (prepared_ && T_ > 0) {
     BeamformerWeights* bw = bf_ptr_->beamformer_weight_object();
-    if (bw && base_ + T_ - 1 >= hist_start_) {
-      std::vector<float> R;
-      csd_state_(base_ + T_ - 1, R);
-      csd_carry_.swap(R);
-    }
+    if (bw && base_ + T_ - 1 >= hist_start_) csd_advance_();
   }
   if (!bf_ptr_->next_block()) return false;
   prepared_ = false; carry_state_ = true; Yhost_valid_ = false;
@@ -2627,10 +2712,11 @@ const void* ZelinskiPostFilter::device_block(long& T, long& T_stride)
   return dYb_.get();
 }
 
+// (the block itself stays where it is: a synthesis bank that took device_block() asks for the base right after)
 long ZelinskiPostFilter::block_base()
 {
-  long T;
-  block(T);
+  if (!has_bf_ptr_) throw j_error("set beamformer's weights \n");
+  if (!prepared_ || bf_version_ != bf_ptr_->weights_version()) compute_(kept_frames(frame_no_, handed_, bf_ptr_->chunk_base(), bf_ptr_->num_frames()));
   return base_;
 }
 
@@ -2669,7 +2755,7 @@ void ZelinskiPostFilter::reset()
   samp_->reset();
   VectorComplexFeatureStream::reset();
   is_end_ = false;
-  prepared_ = false; Yhost_.clear(); Yhost_valid_ = false; T_ = 0; base_ = 0; carry_state_ = false; csd_carry_.clear();
+  prepared_ = false; Yhost_.clear(); Yhost_valid_ = false; T_ = 0; base_ = 0; carry_state_ = false; csd_carry_.clear(); csd_dev_n_ = 0;
   csd_manual_.clear(); manual_frames_ = 0; hist_start_ = 0; handed_ = -1;
   if (!has_bf_ptr_ && dPhi_) {              // manual mode: the densities of the next utterance start from zero
     const unsigned K = fftLen_ / 2 + 1;
@@ -2885,7 +2971,7 @@ void McCowanPostFilter::compute_(long from_frame)
   }
   Yhost_valid_ = false;
   bf_version_ = bf->weights_version();
-  if (!carry) { hist_start_ = base_ + from_frame; csd_carry_.clear(); }
+  if (!carry) { hist_start_ = base_ + from_frame; csd_carry_.clear(); csd_dev_n_ = 0; }
   bind_csd_provider_();
   prepared_ = true;
 }
@@ -3667,13 +3753,16 @@ void SubbandGraphPool::reset()
   }
   rounds_ = 0; base_ = 0; prev_T_ = 0; prev_Lw_ = 0; prev_Lp_ = 0; prev_hist_ = 0; blk_base_ = 0; out_stride_ = 0; first_round_ = true;
   i16_ = false;
+  error_.clear();
 }
 
 // The input of one round: every live graph's banks pull a block of input and the sample windows of all graphs go into one block
 // [G][N][Lmax] of `buf` (rows of 16 bytes for the fused kernel's vector loads, zero behind a shorter -- ending -- stream), copies
 // issued on `stream`.  A graph's windows start their way up as soon as its banks have pulled their input, under the pulling of
 // the next graph: the first graph says how long the rows will be, and only if a later one turns out longer the copies are made
-// again.  Marks graphs whose stream ends with this round as no longer live.
+// again.  Graph::live is left alone: a round may be staged while the one before it is still served, and what its plans say about
+// the end of a stream (plans[g].ended) takes effect when load_round_ makes the round the current one.  st.valid only once all
+// of it is staged: a staging that throws leaves nothing a later call could take for a round.
 void SubbandGraphPool::stage_round_(Stage& st, DeviceBuffer& buf, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -3684,7 +3773,7 @@ void SubbandGraphPool::stage_round_(Stage& st, DeviceBuffer& buf, void* stream_v
   const long q = i16_ ? 8 : 4;                                 // rows of 16 bytes
   st.plans.assign(G, SubbandBeamformer::BlockPlan());
   st.T.assign(G, 0);
-  st.Lmax = 0; st.Tmax = 0; st.t0 = -1; st.f0 = -1; st.valid = true;
+  st.Lmax = 0; st.Tmax = 0; st.t0 = -1; st.f0 = -1; st.valid = false;
   long Lprov = 0;
   char* dPcm = NULL;
   // (the table of the rows' addresses, a segment per graph: no upload of the pool is in flight when a round is staged -- the round
@@ -3714,7 +3803,6 @@ void SubbandGraphPool::stage_round_(Stage& st, DeviceBuffer& buf, void* stream_v
       if (p.L <= Lprov) upload(g, Lprov);
     }
     st.T[g] = p.T;
-    if (p.ended) gr.live = false;
   }
   st.Lmax = (st.Lmax + q - 1) / q * q;
   if (st.Tmax > 0 && st.Lmax != Lprov) {
@@ -3722,11 +3810,25 @@ void SubbandGraphPool::stage_round_(Stage& st, DeviceBuffer& buf, void* stream_v
     dPcm = static_cast<char*>(buf.ensure(es * G * N * st.Lmax));
     for (size_t g = 0; g < G; g++) if (st.T[g] > 0) upload(g, st.Lmax);
   }
+  st.valid = true;
 }
 
 // One round: the staged input (stage_round_ -- staged ahead in a 16-bit stream), one fused launch, one synthesis launch.
-// false: no graph had a frame left.
+// false: no graph had a frame left.  An error is latched (error_): the round it interrupted is lost, so is the lock step.
 bool SubbandGraphPool::load_round_()
+{
+  try {
+    return load_round_unlatched_();
+  } catch (j_error& e) {
+    error_ = e.what();
+    if (i16_) (void)hipStreamSynchronize(cstream());           // copies of a staging that did not complete
+    pre_.valid = false;
+    for (size_t g = 0; g < graphs_.size(); g++) { graphs_[g].has_out = false; graphs_[g].nblocks = 0; graphs_[g].served = 0; }
+    throw;
+  }
+}
+
+bool SubbandGraphPool::load_round_unlatched_()
 {
   const size_t G = graphs_.size();
   if (G == 0) return false;
@@ -3746,7 +3848,9 @@ bool SubbandGraphPool::load_round_()
   Stage cur;
   std::chrono::steady_clock::time_point tu0 = std::chrono::steady_clock::now();
   if (pre_.valid) {
-    // staged while the round before was served (16-bit streams): the copies run on the thread's second stream
+    // staged while the round before was served (16-bit streams): the copies run on the thread's second stream.  The round becomes
+    // the current one only if the sources it was pulled from still are what they were then
+    for (size_t g = 0; g < G; g++) if (graphs_[g].live) graphs_[g].bf->check_i16_sources();
     check_hip(hipStreamSynchronize(cstream()), "hipStreamSynchronize");
     cur = pre_;
     pre_.valid = false;
@@ -3754,6 +3858,7 @@ bool SubbandGraphPool::load_round_()
   } else {
     stage_round_(cur, dPcm_, nstream());
   }
+  for (size_t g = 0; g < G; g++) if (cur.plans[g].ended) graphs_[g].live = false;    // the round is current: so is what it says about the ends
   if (cur.Tmax == 0) return false;                             // (a plan without frames is the end of its stream)
   const std::vector<SubbandBeamformer::BlockPlan>& plans = cur.plans;
   const long Lmax = cur.Lmax, Tmax = cur.Tmax, t0 = cur.t0, f0 = cur.f0;
@@ -3814,6 +3919,7 @@ bool SubbandGraphPool::load_round_()
     check_abi(btk_fb_synthesis(s0->plan(), win, Lw, Lp, (int)G, dO, ostride, bw - lead, nb + lead, nstream()));
     check_hip(hipMemcpy2DAsync(hO, sizeof(float) * nb * D, dO + lead * (long)D, sizeof(float) * ostride, sizeof(float) * nb * D, G,
                                hipMemcpyDeviceToHost, nstream()), "hipMemcpy2DAsync D2H");
+    btk_node_count_d2h(sizeof(float) * nb * D * G);
     nsync();
     for (size_t g = 0; g < G; g++) {
       const int gain = graphs_[g].syn->gain_factor();
@@ -3832,6 +3938,7 @@ bool SubbandGraphPool::load_round_()
 
 bool SubbandGraphPool::next()
 {
+  if (!error_.empty()) throw jconsistency_error("%s", error_.c_str());
   if (graphs_.empty()) return false;
   for (;;) {
     bool any = false;
@@ -3860,6 +3967,7 @@ bool SubbandGraphPool::next()
 
 bool SubbandGraphPool::next_round()
 {
+  if (!error_.empty()) throw jconsistency_error("%s", error_.c_str());
   if (graphs_.empty()) return false;
   for (size_t g = 0; g < graphs_.size(); g++) { graphs_[g].round_first = 0; graphs_[g].round_n = 0; }
   for (;;) {
@@ -4008,6 +4116,7 @@ void FFTFeature::fill_block_()
   check_abi(btk_tdoa_spectra(din, (long)nin, (long)nin, 1, 1, (int)D, (int)fftLen_, window, dout, den, st));
   launches_++;
   check_hip(hipMemcpyAsync(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, st), "FFTFeature download");
+  btk_node_count_d2h(sizeof(float) * nout);
   check_hip(hipStreamSynchronize(st), "FFTFeature block");
   blk_n_ = n;
   blk_pos_ = 0;

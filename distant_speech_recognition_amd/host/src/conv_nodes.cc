@@ -120,6 +120,7 @@ void BlockConvolution::fill_block_()
                              Q_, dout, (long)nout, (long)nout, st));
   launches_++;
   check_hip(hipMemcpyAsync(hout, dout, sizeof(float) * nout, hipMemcpyDeviceToHost, st), "convolution download");
+  btk_node_count_d2h(sizeof(float) * nout);
   check_hip(hipStreamSynchronize(st), "convolution block");
   if (hist) memcpy(tail_.data(), in + nin - hist, sizeof(float) * hist);   // nin >= hist + L: the last P - 1 samples so far
   blk_n_ = n;

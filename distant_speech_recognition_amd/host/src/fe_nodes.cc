@@ -297,14 +297,17 @@ void FeStageNode::fill_chain_(FFTFeature* root)
   // this node's block, and the last frame of every node below it
   float* out = static_cast<float*>(h_out_.ensure(sizeof(float) * (size_t)fe_dim() * (size_t)n));
   check_hip(hipMemcpyAsync(out, dout + at[0], sizeof(float) * (size_t)fe_dim() * (size_t)n, hipMemcpyDeviceToHost, st), "front-end download");
+  btk_node_count_d2h(sizeof(float) * (size_t)fe_dim() * (size_t)n);
   size_t lastN = 2 * K;
   for (size_t i = 1; i < chain.size(); i++) lastN += chain[i]->fe_dim();
   float* last = static_cast<float*>(h_last_.ensure(sizeof(float) * (lastN + 4)));
   check_hip(hipMemcpyAsync(last, dout + (size_t)(n - 1) * 2 * K, sizeof(float) * 2 * K, hipMemcpyDeviceToHost, st), "front-end download");
+  btk_node_count_d2h(sizeof(float) * 2 * K);
   size_t o = 2 * K;
   for (size_t i = 1; i < chain.size(); i++) {
     const size_t d = chain[i]->fe_dim();
     check_hip(hipMemcpyAsync(last + o, dout + at[i] + (size_t)(n - 1) * d, sizeof(float) * d, hipMemcpyDeviceToHost, st), "front-end download");
+    btk_node_count_d2h(sizeof(float) * d);
     o += d;
   }
   check_hip(hipStreamSynchronize(st), "front-end block");
@@ -341,6 +344,7 @@ void FeStageNode::fill_single_()
   launches_++;
   float* out = static_cast<float*>(h_out_.ensure(sizeof(float) * fe_dim()));
   check_hip(hipMemcpyAsync(out, dout, sizeof(float) * fe_dim(), hipMemcpyDeviceToHost, st), "front-end download");
+  btk_node_count_d2h(sizeof(float) * fe_dim());
   check_hip(hipStreamSynchronize(st), "front-end frame");
   blk_n_ = 1;
   blk_pos_ = 0;

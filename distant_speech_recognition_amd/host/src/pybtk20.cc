@@ -770,6 +770,10 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("__len__", &SubbandGraphPool::size)
       .def("rounds", &SubbandGraphPool::rounds)
       .def("is_end", &SubbandGraphPool::is_end, py::arg("g"))
+      // graph g's block of the last next() / next_round() (a view of the pool's buffer); None when that call had none for it
+      .def("output", [](py::object self, unsigned g) -> py::object {
+             const gsl_vector_float* v = self.cast<SubbandGraphPool&>().output(g);
+             return v ? py::object(view(v, self)) : py::object(py::none()); }, py::arg("g"))
       .def("reset", &SubbandGraphPool::reset)
       // one output block per graph: a list with a numpy view of the pool's own buffer per graph, None for a graph that has ended;
       // StopIteration when every graph has ended
@@ -799,6 +803,8 @@ PYBIND11_MODULE(_btk20cpp, m)
              return out; });
   m.def("node_synchronize", []() { btk_node_synchronize(); });     // wait for everything this thread's nodes have launched
   m.def("node_alloc_counts", []() { long d = 0, h = 0; btk_node_alloc_counts(&d, &h); return py::make_tuple(d, h); });   // (hipMalloc, hipHostMalloc) calls so far
+  m.def("node_d2h_bytes", []() { return btk_node_d2h_bytes(); });              // bytes copied device -> host by the nodes since the last reset
+  m.def("node_d2h_bytes_reset", []() { btk_node_d2h_bytes_reset(); });
 
   // ---- dereverberation/dereverberation.h
   py::class_<MultiChannelWPEDereverberation, cref<MultiChannelWPEDereverberation>>(m, "MultiChannelWPEDereverberationPtr")

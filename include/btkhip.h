@@ -310,6 +310,8 @@ int  btk_mvdr_lambda(const void* R, const void* d, void* lambda, int K, int N, f
  * btk_cov_accumulate: R[s][k] += sum_t tf[s][k][t] * fw[s][t] * x x^H  (either weight may be NULL;
  *   pybeamformer.py:979-981, 1087-1093, 1136-1147).  R [dev] complex64 [S][K][N][N].
  *   use_mfma != 0 selects the v_mfma_f32_32x32x2_f32 kernel, 0 the vector-ALU kernel.
+ * btk_cov_scale: R <- float(a * double(R)) on complex64 [S][K][N][N]: the decay step of a recursion R <- a R + sum_t w x x^H
+ *   that stays on the device from block to block (btk_cov_accumulate adds the sum).
  * btk_cov_finalize: R <- R/count, then (gamma > 0) improve_matrix_condition
  *   (pybeamformer.py:994-1000, 1200-1207, 1249-1263); count [dev] [S] or [S][K].                  */
 int  btk_frame_energy(const void* X, int S, int M, int N, long T_stride, long T, float* energy,
@@ -318,6 +320,7 @@ int  btk_cov_frame_gate(const float* energy, const float* label, int S, long T_s
                         float energy_threshold, float* frame_weights, float* frame_count, void* stream);
 int  btk_cov_accumulate(const void* X, const float* tf_weights, const float* frame_weights, void* R,
                         int S, int K, int N, long T_stride, long T, int use_mfma, void* stream);
+int  btk_cov_scale(void* R, double a, int S, int K, int N, void* stream);
 int  btk_cov_finalize(void* R, const float* count, int count_per_bin, int S, int K, int N, float gamma,
                       void* stream);
 
