@@ -247,3 +247,18 @@ def accept(Y, Y32, Ycf, factor=FACTOR):
     ratio = max(r_max, r_bin)
     return bool(ratio <= factor), {"e_max": em, "y_max": ym, "e_bin": float(np.max(eb)), "y_bin": ybm, "ratio": ratio,
                                    "bad_rows": np.nonzero(np.where(over, eb / max(ybm, 1e-300), 0.0) > factor)[0][:8].tolist()}
+
+
+def cfratio_line(label, fig):
+    """The line the GPU modules print per case; their docstring tables are made from these."""
+    return ("CFRATIO %-58s ratio %7.3f  e_max %.3e (f32 %.3e)  e_bin %.3e (f32 %.3e)" %
+            (label, fig["ratio"], fig["e_max"], fig["y_max"], fig["e_bin"], fig["y_bin"]))
+
+
+def judge(label, Y, Y32, Ycf, factor=FACTOR, show=True):
+    """Print the figures, then assert the rule (show=False: print only a case that fails; the caller prints its worst)."""
+    ok, fig = accept(Y, Y32, Ycf, factor)
+    if show or not ok:
+        print(cfratio_line(label, fig))
+    assert ok, (label, fig)
+    return fig
