@@ -4,7 +4,7 @@
 // The arithmetic, the LDS layout and the interior channel loop are those of analysis512_bfz_kernel<2, 33231> in fb_analysis512.hip
 // (see there for the formulation: beamformer sum in the Z domain, one Hermitian post-pass per tile, window loads one channel ahead,
 // weight pairs by LDS-DMA, folded-constant radix-16 passes); that file and fft_packed.h are pinned by the measurement records of
-// bench.py, so what changes at the tile and launch level lives here.  Two things differ:
+// bench.py, so what changes at the tile and launch level lives here.  Three things differ:
 //   * blockIdx -> (stream, tile): the tiles whose span is not wholly inside the recording (the first and the last of every stream
 //     in a whole-utterance launch) take the LOWEST block indices.  They are the slowest workgroups of the launch; dispatched last
 //     (the last tile of the last stream used to be the very last workgroup) they ran alone on a draining chip.  The interior tiles
@@ -15,6 +15,9 @@
 //     pairs) with every window row guarded -- a row (8 bytes at g0 + col + i D) wholly inside the recording is loaded as in the
 //     interior loop, a row wholly outside is zero, and the one row the end of a recording of odd length can cut is one element.
 //     The polyphase sums see the same values in the same order: the bits do not change.
+//   * every window row of a tile's span is loaded once: the workgroup is split by the parity of the span's 23 rows (threads
+//     0..127 the 12 even rows, threads 128..255 the 11 odd ones) instead of by frame half (15 rows each, 7 of them twice).  Every
+//     thread still does 4 taps x 16 outputs with the same operands in the same order.
 // Unaligned or odd-strided PCM keeps the register-staged loop.
 #include "btk_internal.h"
 #include "fft_packed.h"
@@ -33,7 +36,9 @@ static_assert(F_WSTR == FB_WSTR512, "btk_fb_analysis_bf_scratch_bytes sizes the 
 constexpr int F_WQ_OFF = F_FB_BYTES;
 constexpr int F_LDS = F_FB_BYTES + 2 * F_WSTR * 16;                 // frames (the staged loop's span aliases them) + two weight-pair buffers
 constexpr int F_NV4 = (F_SPAN / 4 + F_NT - 1) / F_NT;
-constexpr int F_NPG = 128, F_FPT = 8, F_NWG = F_FPT + (F_MT - 1) * 2 + 1;   // pair indices n0, n0 + 128; 8 frames per thread; 15 window rows
+constexpr int F_NPG = 128, F_FPT = 8;                                // pair indices n0, n0 + 128; 8 outputs of each per thread
+constexpr int F_NROW = F_TT - 1 + 2 * (F_MT - 1) + 2;                 // 23 window rows (of D samples) under a tile
+constexpr int F_NWG = (F_NROW + 1) / 2;                              // 12 even rows; the odd half of the workgroup takes the 11 odd ones
 static_assert(F_SPAN * 4 <= F_FB_BYTES, "the staged span shares the frame region");
 
 enum { LOOP_INTERIOR = 0, LOOP_EDGE = 1, LOOP_STAGED = 2 };
@@ -49,7 +54,7 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
                      float2* __restrict__ Y, long T_stride, long t0, long tcount, int ntiles, int tile_lo, int tile_hi,
                      int tiles_per_xcd, int S)
 {
-  constexpr int D = F_D, NWG = F_NWG, FPT = F_FPT, NPG = F_NPG;
+  constexpr int D = F_D, NWG = F_NWG, FPT = F_FPT, NPG = F_NPG, NROW = F_NROW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* xs = reinterpret_cast<float*>(smem);                                 // staged loop only: the PCM span, overwritten by the frames
   float2* fbuf = reinterpret_cast<float2*>(smem);
@@ -107,10 +112,13 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
     w256pre = make_float2(t.x, t.y);
   };
 
-  // polyphase mapping: the windows of the pair indices n and n + D/2 are the same words shifted by one frame, so a thread
-  // takes the two indices n0, n0 + 128 for half of the tile's frames and reads every word once
-  const int n0 = tid % NPG, fg = tid / NPG;
-  const int wo = (F_M - 2 - 2 * n0 - F_M / 2) + fg * FPT * D;                  // first window row of this thread within the span
+  // polyphase mapping: output (pair index n0 + q 128, frame f, tap k) reads row f + 2 (m-1-k) + (1-q) of the span's 23 rows at
+  // column wo, and the parity of that row is the parity of f + 1 - q whatever the tap.  The workgroup is split by row parity:
+  // threads 0..127 load the 12 even rows and produce {q = 1, f even} and {q = 0, f odd}, threads 128..255 load the 11 odd rows
+  // and produce {q = 1, f odd} and {q = 0, f even}: every word of the span is loaded once per tile, 16 outputs per thread.
+  // A wavefront is all-even or all-odd, and the channel loop is instantiated for either parity (register rows are compile-time).
+  const int n0 = tid % NPG;
+  const int wo = F_M - 2 - 2 * n0 - F_M / 2;                                  // this thread's column within a row of the span
   float2 h[2][F_MT];
 #pragma unroll
   for (int q = 0; q < 2; q++)
@@ -169,51 +177,54 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
   // unaligned launch (guarded element loads, four barriers, compiler-managed waits).  One loop with runtime branches let hipcc
   // hoist the guarded loads above the branch.
   float2 win[NWG];                            // polyphase window of the channel about to be transformed (loaded a channel ahead)
-  auto channels = [&](auto loop_kind) {
+  auto channels = [&](auto loop_kind, auto parity) {
   constexpr int LOOP = decltype(loop_kind)::value;
+  constexpr int PAR = decltype(parity)::value;                  // win[i] = row PAR + 2 i of the span
+  constexpr int NLD = (NROW - PAR + 1) / 2;                     // 12 even / 11 odd rows
   constexpr bool DIRECT = LOOP != LOOP_STAGED;
   if constexpr (!DIRECT) asm volatile("" : "+s"(pcm_e), "+s"(wts_e));
-  // edge loop: which of this thread's window rows lie wholly inside the recording, and the one row its end may cut.  Row i starts
-  // at g0 + wo + i D = base + i D + c with base = g0 + fg FPT D a multiple of D (wave-uniform) and c = 254 - 2 n0 even, in [0, D):
-  // the start of the recording never cuts a row and the rows in front of it are the same for the whole wavefront (i < row_lo); the
-  // end leaves rem samples from this thread's row 0: row i is whole when i D + 1 < rem and cut when i D + 1 == rem (nsamples odd).
+  // edge loop: which rows of the span lie wholly inside the recording at this thread's column, and the one row its end may cut.
+  // Row r starts at g0 + r D + c with g0 a multiple of D (uniform) and c = wo = 254 - 2 n0 even, in [0, D): the start of the
+  // recording never cuts a row and the rows in front of it are the same for every thread (r < row_lo); the end leaves rem samples
+  // from this thread's column in row 0: row r is whole when r D + 1 < rem and cut when r D + 1 == rem (nsamples odd).
   int row_lo = 0, rem = 0;
   if constexpr (LOOP == LOOP_EDGE) {
-    const long base = g0 + (long)__builtin_amdgcn_readfirstlane(fg) * FPT * D;
-    row_lo = base >= 0 ? 0 : (-base / D < NWG ? (int)(-base / D) : NWG);
-    const long left = nsamples - base - (F_M / 2 - 2 - 2 * n0);
-    rem = left < 0 ? 0 : (left > NWG * D ? NWG * D : (int)left);
+    row_lo = g0 >= 0 ? 0 : (-g0 / D < NROW ? (int)(-g0 / D) : NROW);
+    const long left = nsamples - g0 - wo;
+    rem = left < 0 ? 0 : (left > NROW * D ? NROW * D : (int)left);
   }
-  auto row_full = [&](int i) { return i >= row_lo && i * D + 1 < rem; };
-  auto row_cut = [&](int i) { return i >= row_lo && i * D + 1 == rem; };
-  // V[i] of channel n straight from HBM / L2 (8-byte loads, 512 contiguous bytes per wave-instruction)
+  auto row_full = [&](int r) { return r >= row_lo && r * D + 1 < rem; };
+  auto row_cut = [&](int r) { return r >= row_lo && r * D + 1 == rem; };
+  // rows PAR, PAR + 2, ... of channel n straight from HBM / L2 (8-byte loads, 512 contiguous bytes per wave-instruction)
   auto wload = [&](float2 (&win)[NWG], int n) {
     const PT* wsrc = pcm + ((long)s * N + n) * pcm_stride + g0 + wo;
     if constexpr (I16) {
-      // 15 four-byte TYPED buffer loads: the load unit delivers the two samples as floats (btk_internal.h)
+      // four-byte TYPED buffer loads: the load unit delivers the two samples as floats (btk_internal.h)
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<PT*>(pcm + ((long)s * N + n) * pcm_stride + g0), 0, 0x7fffffff,
                                                                           BTK_RSRC_I16X2_SSCALED);
       const int vo = wo * 2;
 #pragma unroll
-      for (int i = 0; i < NWG; i++) {
+      for (int i = 0; i < NLD; i++) {
+        const int r = PAR + 2 * i;
         if constexpr (LOOP == LOOP_INTERIOR) {
-          const btk_f2v t = btk_buffer_load_i16x2_f32(rs, vo, i * D * 2, 0); win[i] = make_float2(t.x, t.y);
+          const btk_f2v t = btk_buffer_load_i16x2_f32(rs, vo, r * D * 2, 0); win[i] = make_float2(t.x, t.y);
         } else {
           float2 v = make_float2(0.f, 0.f);
-          if (row_full(i)) { const btk_f2v t = btk_buffer_load_i16x2_f32(rs, vo, i * D * 2, 0); v = make_float2(t.x, t.y); }
-          else if (row_cut(i)) v.x = (float)wsrc[i * D];
+          if (row_full(r)) { const btk_f2v t = btk_buffer_load_i16x2_f32(rs, vo, r * D * 2, 0); v = make_float2(t.x, t.y); }
+          else if (row_cut(r)) v.x = (float)wsrc[r * D];
           win[i] = v;
         }
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < NWG; i++) {
+      for (int i = 0; i < NLD; i++) {
+        const int r = PAR + 2 * i;
         if constexpr (LOOP == LOOP_INTERIOR) {
-          win[i] = *reinterpret_cast<const float2*>(wsrc + i * D);
+          win[i] = *reinterpret_cast<const float2*>(wsrc + r * D);
         } else {
           float2 v = make_float2(0.f, 0.f);
-          if (row_full(i)) v = *reinterpret_cast<const float2*>(wsrc + i * D);
-          else if (row_cut(i)) v.x = (float)wsrc[i * D];
+          if (row_full(r)) v = *reinterpret_cast<const float2*>(wsrc + r * D);
+          else if (row_cut(r)) v.x = (float)wsrc[r * D];
           win[i] = v;
         }
       }
@@ -235,12 +246,13 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
 
     // the polyphase stage -- 64 packed instructions between the channel's two barriers -- runs at wave priority 1 (fb_analysis512.hip)
     __builtin_amdgcn_s_setprio(1);
-    // ---- phase 2: polyphase (sliding register window).  index n0 + q NPG, frame f0 + g, tap k uses V[g + 2 (m-1-k) + (1-q)]
+    // ---- phase 2: polyphase (sliding register window).  index n0 + q NPG, frame f = 2 u + ((PAR + q + 1) & 1), tap k uses row
+    //      f + 2 (m-1-k) + (1-q) = PAR + 2 i of the span
     {
       if constexpr (!DIRECT) {
         const float* wbase = xs + wo;
 #pragma unroll
-        for (int i = 0; i < NWG; i++) win[i] = *reinterpret_cast<const float2*>(wbase + i * D);
+        for (int i = 0; i < NLD; i++) win[i] = *reinterpret_cast<const float2*>(wbase + (PAR + 2 * i) * D);
         __syncthreads();                                   // the frames overwrite the span
       }
       // tap-major order: consecutive FMAs belong to different outputs (no dependent back-to-back packed FMAs)
@@ -251,18 +263,20 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
 #pragma unroll
         for (int q = 0; q < 2; q++)
 #pragma unroll
-          for (int g = 0; g < FPT; g++) {
-            const float2 xw = win[g + 2 * (F_MT - 1 - k) + (1 - q)];
+          for (int u = 0; u < FPT; u++) {
+            const int f = 2 * u + ((PAR + q + 1) & 1);
+            const float2 xw = win[(f + 2 * (F_MT - 1 - k) + (1 - q) - PAR) / 2];
             const f2 x = f2{xw.x, xw.y}, hk = f2{h[q][k].x, h[q][k].y};
-            if (k == 0) po[q][g] = pk_mul_xswap(hk, x);
-            else pk_fma_xswap(po[q][g], hk, x);
+            if (k == 0) po[q][u] = pk_mul_xswap(hk, x);
+            else pk_fma_xswap(po[q][u], hk, x);
           }
+      // frame by frame: index n0 + 128 of a frame and index n0 of the next one are 136 float2 apart (one ds_write2_b64)
+      const int zoff = (n0 >> 4) * 17 + (n0 & 15);
+      constexpr int ZQ = (NPG >> 4) * 17;
 #pragma unroll
-      for (int q = 0; q < 2; q++) {
-        const int nn = n0 + q * NPG;
-        const int zoff = (nn >> 4) * 17 + (nn & 15);
-#pragma unroll
-        for (int g = 0; g < FPT; g++) fbuf[(fg * FPT + g) * F_FRZ + zoff] = make_float2(po[q][g].x, po[q][g].y);
+      for (int f = 0; f < F_TT; f++) {
+        const int q = (f + 1 + PAR) & 1, u = f >> 1;
+        fbuf[f * F_FRZ + zoff + q * ZQ] = make_float2(po[q][u].x, po[q][u].y);
       }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -325,8 +339,8 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
     }
     if constexpr (LOOP == LOOP_INTERIOR) {
 #pragma unroll
-      for (int i = 0; i < NWG; i++) {
-        __builtin_amdgcn_sched_group_barrier(0x080, 3, 0);    // three LDS instructions (anchors: the FFT's data flow fixes their order) ...
+      for (int i = 0; i < NLD; i++) {
+        __builtin_amdgcn_sched_group_barrier(0x080, 4, 0);    // four LDS instructions (anchors: the FFT's data flow fixes their order) ...
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);    // ... then one window load
       }
     }
@@ -336,11 +350,15 @@ void fused512_kernel(const PT* __restrict__ pcm, long nsamples, long pcm_stride,
   else { dma(0); wload(win, 0); }
   for (int n = 0; n < N; n++) body(n, win);
   };
+  auto both_parities = [&](auto loop_kind) {
+    if (__builtin_amdgcn_readfirstlane(tid / NPG) == 0) channels(loop_kind, std::integral_constant<int, 0>{});
+    else channels(loop_kind, std::integral_constant<int, 1>{});
+  };
   if (vec_ok) {
-    if (inside) channels(std::integral_constant<int, LOOP_INTERIOR>{});
-    else channels(std::integral_constant<int, LOOP_EDGE>{});
+    if (inside) both_parities(std::integral_constant<int, LOOP_INTERIOR>{});
+    else both_parities(std::integral_constant<int, LOOP_EDGE>{});
   } else {
-    channels(std::integral_constant<int, LOOP_STAGED>{});
+    both_parities(std::integral_constant<int, LOOP_STAGED>{});
   }
 
   __syncthreads();
