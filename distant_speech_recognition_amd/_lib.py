@@ -32,6 +32,9 @@ BTK_ERR_NUMERIC = -6
 BTK_AEC_FRAME_CONTINUE = -(1 << 30)  # frame_no0 of btk_aec_process: count up from the state's frames done
 BTK_TDOA_NO_PEAK = -(1 << 31)        # lag of btk_tdoa_gcc_peaks where a frame has no peak (include/btkhip.h)
 BTK_PF_MCCOWAN_RULES = 0x10      # type bit of btk_zelinski_process (include/btkhip.h)
+BTK_SS_TRAIN, BTK_SS_SUBTRACT = 1, 2     # frame flags / mode bits of btk_ss_process
+BTK_WIENER_UPDATE_NOISE = 1              # frame flag / mode bit of btk_wiener_process
+BTK_SS_FORM_AUTO, BTK_SS_FORM_ROWS = 0, 1
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
@@ -166,6 +169,14 @@ SIGNATURES = {
     "btk_conv_filter_spectra": (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
     "btk_conv_apply": (_i, [_vp, _l, _l, _l, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _l, _l, _vp]),
     "btk_conv_blocks": (_i, [_vp, _l, _l, _i, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # single-channel enhancement: SpectralSubtractor / AveragePSDEstimator / WienerFilter (postfilter/spectralsubtraction.cc:57-129,
+    # :216-285, :314-362) and HighPassFilter (postfilter/postfilter.cc:1215-1239)
+    "btk_ss_max_channels": (_i, []),
+    "btk_ss_process": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _vp, _i, _d, _d, _vp, _l, _vp, _vp, _vp, _vp, _i, _vp]),
+    "btk_ss_finish_training": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "btk_ss_clear": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "btk_wiener_process": (_i, [_vp, _vp, _vp, _i, _i, _l, _l, _vp, _i, _d, _d, _d, _l, _vp, _vp, _vp]),
+    "btk_spec_highpass": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _vp]),
 }
 
 

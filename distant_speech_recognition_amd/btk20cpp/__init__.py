@@ -156,6 +156,7 @@ OverSampledDFTAnalysisBank, OverSampledDFTSynthesisBank = _mod.OverSampledDFTAna
 SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _mod.SubbandGSCRLSPtr
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
 ZelinskiPostFilter, McCowanPostFilter, LefkimmiatisPostFilter = _mod.ZelinskiPostFilterPtr, _mod.McCowanPostFilterPtr, _mod.LefkimmiatisPostFilterPtr
+SpectralSubtractor, WienerFilter, HighPassFilter = _mod.SpectralSubtractorPtr, _mod.WienerFilterPtr, _mod.HighPassFilterPtr
 DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA = _mod.DOAEstimatorSRPBasePtr, _mod.DOAEstimatorSRPDSBLAPtr
 NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature = _mod.NLMSAcousticEchoCancellationFeaturePtr, _mod.KalmanFilterEchoCancellationFeaturePtr
 BlockKalmanFilterEchoCancellationFeature = _mod.BlockKalmanFilterEchoCancellationFeaturePtr
@@ -167,4 +168,4 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
             "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
             "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
-            "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave"]
+            "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter", "HighPassFilter"]

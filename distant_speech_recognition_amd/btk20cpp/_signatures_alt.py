@@ -46,6 +46,9 @@ CLASS_METHOD_KWARGS = {
 }
 
 CTOR_KWARGS = {
+    # the class spells them cutOffFreq / sampleRate, the .i file cut_off_freq / samplerate (the generated table); these are the class's;
+    # 150 is postfilter.i:298's default
+    'HighPassFilterPtr': [('output', None), ('cutOffFreq', 150.0), ('sampleRate', None), ('nm', 'HighPassFilter')],
     'OverlapAddPtr': [('samp', None), ('impulse_response', None), ('fft_len', 0), ('nm', 'Overlap Add')],
     'OverlapSavePtr': [('samp', None), ('impulse_response', None), ('nm', 'Overlap Save')],
     'LefkimmiatisPostFilterPtr': [('output', None), ('fftlen', None), ('min_sv', 1e-08), ('fbin_no1', 0), ('alpha', 0.6), ('type', 2), ('min_frames', 0), ('threshold', 0.99), ('nm', 'LefkimmiatisPostFilterPtr')],
@@ -62,6 +65,9 @@ ALIASES = {
     'MultiChannelWPEDereverberationPtr': {'setInput': 'set_input', 'nextSpeaker': 'next_speaker'},
     'SingleChannelWPEDereverberationFeaturePtr': {'nextSpeaker': 'next_speaker'},
     'SnapShotArrayPtr': {'fftlen': 'fftLen', 'chan_num': 'nChan'},
+    # postfilter.i declares the subtractor under both spellings and WienerFilter's setters under the legacy names only
+    'SpectralSubtractorPtr': {'setNoiseOverEstimationFactor': 'set_noise_over_estimation_factor', 'setChannel': 'set_channel', 'startTraining': 'start_training', 'stopTraining': 'stop_training', 'clearNoiseSamples': 'clear_noise_samples', 'startNoiseSubtraction': 'start_noise_subtraction', 'stopNoiseSubtraction': 'stop_noise_subtraction', 'readNoiseFile': 'read_noise_file', 'writeNoiseFile': 'write_noise_file'},
+    'WienerFilterPtr': {'setNoiseAmplificationFactor': 'set_noise_amplification_factor', 'startUpdatingNoisePSD': 'start_updating_noise_PSD', 'stopUpdatingNoisePSD': 'stop_updating_noise_PSD'},
     'SubbandDSPtr': {'calcArrayManifoldVectors': 'calc_array_manifold_vectors'},
     'SubbandGSCPtr': {'calcGSCWeights': 'calc_gsc_weights', 'setActiveWeights_f': 'set_active_weights_f', 'getBlockingMatrix': 'blocking_matrix'},
     'SubbandGSCRLSPtr': {'initPrecisionMatrix': 'init_precision_matrix', 'setPrecisionMatrix': 'set_precision_matrix', 'updateActiveWeightVecotrs': 'update_active_weight_vecotrs', 'setQuadraticConstraint': 'set_quadratic_constraint'},

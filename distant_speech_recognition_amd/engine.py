@@ -9,6 +9,7 @@ hand-written HIP kernel in csrc/.  Tensor layouts:
 import collections
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import torch
@@ -982,6 +983,187 @@ def bf_apply_lefkimmiatis(W, D, X, state, fbin_x1=0, alpha=0.6, type_=2, min_fra
                                      int(type_), int(min_frames), state.frames_done, _ptr(state.u), _ptr(state.v),
                                      _ptr(state.w_last), _stream()))
     state.frames_done += T
+    return out
+
+
+# ---------------------------------------------------------------------------- spectral subtraction, Wiener filter, high-pass
+def _frame_flags(flags, T, device, name):
+    """uint8 [T] device tensor of per-frame mode bits (or None): a host sequence is uploaded."""
+    if flags is None:
+        return None
+    if not torch.is_tensor(flags):
+        flags = torch.from_numpy(np.ascontiguousarray(flags, dtype=np.uint8)).to(device)
+    _check(flags, name, torch.uint8, (T,))
+    return flags
+
+
+class SpectralSubtractionState:
+    """Noise models of S spectral subtractors with C channels each (the AveragePSDEstimator of every set_channel(),
+    postfilter/spectralsubtraction.cc:52-129, :185-189), bins 0..M/2.  alphas: one forgetting factor per channel, < 0 for a channel
+    that averages its training frames (the reference's default, -1).  est, acc float64 [S][C][K]; count int64 [S][C] (frames in
+    acc, averaging channels); added uint8 [S][C] (sample_added_, recursive channels); frames_done places the scan chunks."""
+
+    def __init__(self, S, C, M, alphas=None, device="cuda"):
+        self.S, self.C, self.M, self.Kb = int(S), int(C), int(M), int(M) // 2 + 1
+        if self.S < 1 or self.M < 2 or self.M % 2 or self.M > 2048:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "SpectralSubtractionState: S=%d M=%d" % (S, M))
+        if not 1 <= self.C <= _lib.lib().btk_ss_max_channels():
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "SpectralSubtractionState: %d channels" % C)
+        a = np.full(self.C, -1.0) if alphas is None else np.array(alphas, np.float64).reshape(-1)
+        if a.shape != (self.C,):
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "SpectralSubtractionState: %d alphas for %d channels" % (a.size, self.C))
+        self.alphas = np.ascontiguousarray(a)
+        dev = torch.device(device)
+        self.est = torch.zeros((self.S, self.C, self.Kb), dtype=torch.float64, device=dev)
+        self.acc = torch.zeros((self.S, self.C, self.Kb), dtype=torch.float64, device=dev)
+        self.count = torch.zeros((self.S, self.C), dtype=torch.int64, device=dev)
+        self.added = torch.zeros((self.S, self.C), dtype=torch.uint8, device=dev)
+        self.frames_done = 0
+
+    def _clear(self, what):
+        check(_lib.lib().btk_ss_clear(self.S, self.M, self.C, what, _ptr(self.acc), _ptr(self.count), _ptr(self.added), _stream()))
+
+    def reset_training(self):
+        """clear_noise_samples() (:198-202): the averaging sums and their frame counts go, the estimates stay."""
+        self._clear(0)
+
+    def clear(self):
+        """AveragePSDEstimator::clear() (:63-68): as reset_training(), and the next training frame of a recursive channel is a first
+        sample again.  The estimates stay until then."""
+        self._clear(1)
+
+    def finish_training(self):
+        """stop_training()'s average() (:70-87, :191-196): est = acc (1.0/(float)count) on the averaging channels."""
+        check(_lib.lib().btk_ss_finish_training(self.S, self.M, self.C, _np_ptr(self.alphas), _ptr(self.est), _ptr(self.acc),
+                                                _ptr(self.count), _stream()))
+
+    def noise_psd(self):
+        """A copy of the noise PSD estimates, float64 [S][C][K]."""
+        return self.est.clone()
+
+    def set_noise_psd(self, psd, channel=None):
+        """Overwrite the estimates (read_estimates, :29-50): psd [K] or [S][K] for one channel, [S][C][K] without `channel`."""
+        psd = torch.as_tensor(psd, dtype=torch.float64).to(self.est.device)
+        if channel is None:
+            self.est.copy_(psd.expand_as(self.est))
+        else:
+            self.est[:, int(channel)].copy_(psd.expand(self.S, self.Kb))
+
+    def write_noise_file(self, fn, channel=0, stream=0):
+        """write_noise_file (spectralsubtraction.h:89): one channel's estimate of one stream, see write_noise_psd_file."""
+        return write_noise_psd_file(fn, self.est[int(stream), int(channel)].cpu().numpy())
+
+    def read_noise_file(self, fn, channel=0, stream=None):
+        """read_estimates (:17-33) into one channel's estimate (of every stream, or of `stream`); False where the file cannot be
+        opened, as there.  (That training ends with it, :204-207, is the caller's mode.)"""
+        psd = read_noise_psd_file(fn, self.Kb)
+        if psd is None:
+            return False
+        row = torch.from_numpy(psd).to(self.est.device)           # a short file names the first bins only: the others stay
+        if stream is None:
+            self.est[:, int(channel), : len(psd)] = row
+        else:
+            self.est[int(stream), int(channel), : len(psd)] = row
+        return True
+
+
+def write_noise_psd_file(fn, psd):
+    """PSDEstimator::write_estimates (spectralsubtraction.cc:35-49): the reference's text format, "%lf\\n" per bin, K lines.  The
+    six decimals are part of it: a model read back holds each bin to within 5e-7."""
+    try:
+        with open(fn, "w") as fp:
+            fp.write("".join("%f\n" % v for v in np.asarray(psd, np.float64).reshape(-1)))
+    except OSError:
+        sys.stderr.write("could not write %s\n" % fn)
+        return False
+    return True
+
+
+def read_noise_psd_file(fn, K):
+    """PSDEstimator::read_estimates (:17-33): the file's values, float64, at most K of them; None where the file cannot be
+    opened.  A file with fewer than K lines yields a shorter array: the reference leaves the bins it does not name as they were,
+    and so does SpectralSubtractionState.read_noise_file."""
+    try:
+        with open(fn) as fp:
+            vals = [float(v) for v in fp.read().split()][:K]
+    except OSError:
+        sys.stderr.write("could not read %s\n" % fn)
+        return None
+    return np.array(vals, np.float64)
+
+
+def spectral_subtract(X, state, ft=1.0, floor=0.001, flags=None, train=False, subtract=True, out=None, form=None):
+    """Spectral subtraction over a block (SpectralSubtractor::next, :216-285): X complex64 [S][K][C][T] (rows may be padded) ->
+    Y [S][K][T], the mean over the channels of X sqrt(max(|X|^2 - ft est, floor))/|X|; state updated in place.
+    flags: uint8 [T], bit 0 (BTK_SS_TRAIN) the frame enters the noise model -- before it is subtracted --, bit 1 (BTK_SS_SUBTRACT)
+    the frame is subtracted; without flags every frame has the mode (train, subtract).  A block that cannot train runs frame-
+    parallel; form=_lib.BTK_SS_FORM_ROWS forces the row scan (same bits)."""
+    ts = _check(X, "X", torch.complex64, (state.S, state.Kb, state.C, None), rows=True)
+    S, K, C, T = X.shape
+    if out is None:
+        out = rows_like(X, (S, K, T))
+    elif _check(out, "out", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "spectral_subtract: out must share the row stride of X")
+    flags = _frame_flags(flags, T, X.device, "flags")
+    mode = (_lib.BTK_SS_TRAIN if train else 0) | (_lib.BTK_SS_SUBTRACT if subtract else 0)
+    check(_lib.lib().btk_ss_process(_ptr(X), _ptr(out), S, state.M, C, ts, T, None if flags is None else _ptr(flags), mode,
+                                    float(ft), float(floor), _np_ptr(state.alphas), state.frames_done, _ptr(state.est),
+                                    _ptr(state.acc), _ptr(state.count), _ptr(state.added),
+                                    _lib.BTK_SS_FORM_AUTO if form is None else int(form), _stream()))
+    state.frames_done += T
+    return out
+
+
+class WienerState:
+    """Recursively averaged target and noise PSDs of S Wiener filters (prev_PSDs_, prev_PSDn_, spectralsubtraction.cc:304-305),
+    float64 [S][K] (row 0 is never touched), and the frame counter that decides the two frames without memory.  reset() of the
+    node resets its sources only (:364-368): there is nothing to reset here."""
+
+    def __init__(self, S, M, device="cuda"):
+        self.S, self.M, self.Kb = int(S), int(M), int(M) // 2 + 1
+        if self.S < 1 or self.M < 2 or self.M % 2 or self.M > 2048:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "WienerState: S=%d M=%d" % (S, M))
+        self.psd_s = torch.zeros((self.S, self.Kb), dtype=torch.float64, device=torch.device(device))
+        self.psd_n = torch.zeros_like(self.psd_s)
+        self.frames_done = 0
+
+
+def wiener_filter(Sx, Nx, state, alpha=0.0, floor=0.001, beta=1.0, flags=None, update_noise=True, out=None):
+    """Wiener filter over a block (WienerFilter::next, :314-362): target Sx, noise Nx complex64 [S][K][T] (rows may be padded) ->
+    Y = H Sx, H = PSDs/(PSDs + beta PSDn); bin 0 is Sx's.  flags: uint8 [T], bit 0 (BTK_WIENER_UPDATE_NOISE) the frame updates the
+    noise PSD; without flags update_noise holds for every frame."""
+    ts = _check(Sx, "Sx", torch.complex64, (state.S, state.Kb, None), rows=True)
+    S, K, T = Sx.shape
+    if _check(Nx, "Nx", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "wiener_filter: Sx and Nx must share one row stride")
+    if out is None:
+        out = rows_like(Sx, (S, K, T))
+    elif _check(out, "out", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "wiener_filter: out must share the row stride of Sx")
+    flags = _frame_flags(flags, T, Sx.device, "flags")
+    check(_lib.lib().btk_wiener_process(_ptr(Sx), _ptr(Nx), _ptr(out), S, state.M, ts, T, None if flags is None else _ptr(flags),
+                                        _lib.BTK_WIENER_UPDATE_NOISE if update_noise else 0, float(alpha), float(floor),
+                                        float(beta), state.frames_done, _ptr(state.psd_s), _ptr(state.psd_n), _stream()))
+    state.frames_done += T
+    return out
+
+
+def highpass_cutoff_bin(M, cut_off_freq, samplerate):
+    """HighPassFilter's cut-off bin (postfilter/postfilter.cc:1206-1213): (unsigned)(M cutOffFreq/(float)sampleRate) in float32."""
+    return int(np.float32(M) * np.float32(cut_off_freq) / np.float32(samplerate))
+
+
+def spec_highpass(X, cutoff_bin, out=None):
+    """Spectral high-pass (HighPassFilter::next, postfilter/postfilter.cc:1215-1239): X complex64 [S][K][T] (rows may be padded) ->
+    Y with bins 0 .. cutoff_bin-1 zero (DC included: the reference never writes it) and the others copied.  cutoff_bin = 0, with
+    which the reference writes outside its vector, copies every bin.  out may be X."""
+    ts = _check(X, "X", torch.complex64, 3, rows=True)
+    S, K, T = X.shape
+    if out is None:
+        out = rows_like(X, (S, K, T))
+    elif _check(out, "out", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "spec_highpass: out must share the row stride of X")
+    check(_lib.lib().btk_spec_highpass(_ptr(X), _ptr(out), S, 2 * (K - 1), int(cutoff_bin), ts, T, _stream()))
     return out
 
 

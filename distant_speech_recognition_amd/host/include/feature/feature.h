@@ -29,6 +29,7 @@ class SampleFeature : public VectorFloatFeatureStream {
   // [-1, 1) values divided by that norm first (feature.cc:429-518)
   void write(const String& fn, int format = sndfile::SF_FORMAT_WAV | sndfile::SF_FORMAT_PCM_16, int sampleRate = -1);
   void cut(unsigned cfrom, unsigned cto);
+  bool isEnd() { return is_end(); }                     // src/ss.cc:247 calls it (the reference's own header lost it)
   void randomize(int startX, int endX, double sigma2);
   virtual const gsl_vector_float* next(int frame_no = -5);
   virtual void reset() { cur_ = 0; VectorFloatFeatureStream::reset(); is_end_ = false; }

@@ -137,3 +137,19 @@ class LefkimmiatisPostFilter : public McCowanPostFilter {
   virtual const char* no_R_msg_() const { return "LefkimmiatisPostFilter:  construct/set a noise coherence matrix\n"; }
 };
 typedef Inherit<LefkimmiatisPostFilter, McCowanPostFilterPtr> LefkimmiatisPostFilterPtr;
+
+// High-pass filter in the subband domain (reference postfilter/postfilter.h:205-219, postfilter.cc:1203-1244) through
+// btk_spec_highpass: bins 0 .. cutoff-1 are zero (the reference never writes bin 0, so DC goes too), bins cutoff .. M/2 are the
+// source's, cutoff = (unsigned)(fftLen * cutOffFreq / (float)sampleRate).  Stated deviation: cutoff = 0 makes the reference write
+// vector_[M], out of range; here it copies all M/2 + 1 bins.  A block node (postfilter/enhancement_node.h).
+#include "postfilter/enhancement_node.h"
+class HighPassFilter : public EnhancementBlockNode_ {
+ public:
+  HighPassFilter(VectorComplexFeatureStreamPtr& output, float cutOffFreq, int sampleRate, const String& nm = "HighPassFilter");
+  unsigned cutoff_bin() const { return cutoff_fbinX_; }
+ protected:
+  virtual void launch_(const void* dX, void* dOut, long Ts, long t0, long t1, long frames_done);
+ private:
+  unsigned cutoff_fbinX_;
+};
+typedef Inherit<HighPassFilter, VectorComplexFeatureStreamPtr> HighPassFilterPtr;

@@ -23,6 +23,7 @@
 #include "feature/feature.h"
 #include "modulated/modulated.h"
 #include "postfilter/postfilter.h"
+#include "postfilter/spectralsubtraction.h"
 
 namespace py = pybind11;
 typedef std::complex<double> cd;
@@ -883,4 +884,63 @@ PYBIND11_MODULE(_btk20cpp, m)
            }), py::arg("played"), py::arg("recorded"), py::arg("sample_num") = 1, py::arg("beta") = 0.95, py::arg("sigmau2") = 10e-4,
            py::arg("sigmak2") = 5.0, py::arg("snr_threshold") = 2.0, py::arg("energy_threshold") = 100.0, py::arg("smooth") = 0.9,
            py::arg("amp4play") = 1.0, py::arg("nm") = "DTDBlockKFEchoCanceller");
+
+  // ---- postfilter/spectralsubtraction.h, HighPassFilter of postfilter/postfilter.h (keyword names: postfilter/postfilter.i)
+  py::class_<EnhancementBlockNode_, VectorComplexFeatureStream, cref<EnhancementBlockNode_>>(m, "EnhancementBlockNode")
+      .def("set_block_frames", &EnhancementBlockNode_::set_block_frames, py::arg("n"))
+      .def("block_frames", &EnhancementBlockNode_::block_frames)
+      .def("block_version", [](EnhancementBlockNode_& n) { return n.block_version(); })
+      .def("advance_to", [](EnhancementBlockNode_& n, long frame_idx) { n.advance_to(frame_idx); }, py::arg("frame_idx"))
+      .def("block", [](EnhancementBlockNode_& n) { return block_of(n); });
+  py::class_<SpectralSubtractor, EnhancementBlockNode_, cref<SpectralSubtractor>>(m, "SpectralSubtractorPtr")
+      .def(py::init([](unsigned fftLen, bool halfBandShift, float ft, float flooringV, const std::string& nm) {
+             return new SpectralSubtractor(fftLen, halfBandShift, ft, flooringV, nm);
+           }), py::arg("fftLen"), py::arg("halfBandShift") = false, py::arg("ft") = 1.0f, py::arg("flooringV") = 0.001f,
+           py::arg("nm") = "SpectralSubtractor")
+      .def("clear", &SpectralSubtractor::clear)
+      .def("set_noise_over_estimation_factor", &SpectralSubtractor::set_noise_over_estimation_factor, py::arg("ft"))
+      .def("set_channel", [](SpectralSubtractor& s, py::object chan, double alpha) { VectorComplexFeatureStreamPtr p = as_cstream(chan); s.set_channel(p, alpha); },
+           py::arg("chan"), py::arg("alpha") = -1.0)
+      .def("start_training", &SpectralSubtractor::start_training)
+      .def("stop_training", &SpectralSubtractor::stop_training)
+      .def("clear_noise_samples", &SpectralSubtractor::clear_noise_samples)
+      .def("start_noise_subtraction", &SpectralSubtractor::start_noise_subtraction)
+      .def("stop_noise_subtraction", &SpectralSubtractor::stop_noise_subtraction)
+      .def("read_noise_file", [](SpectralSubtractor& s, const std::string& fn, unsigned idx) { return s.read_noise_file(fn, idx); }, py::arg("fn"), py::arg("idx") = 0)
+      .def("write_noise_file", [](SpectralSubtractor& s, const std::string& fn, unsigned idx) { return s.write_noise_file(fn, idx); }, py::arg("fn"), py::arg("idx") = 0)
+      .def("noise_psd", [](SpectralSubtractor& s, unsigned idx) {
+             const std::vector<double> r = s.noise_psd(idx);
+             py::array_t<double> a((py::ssize_t)r.size());
+             memcpy(a.mutable_data(), r.data(), sizeof(double) * r.size());
+             return a;
+           }, py::arg("idx") = 0);
+  py::class_<WienerFilter, EnhancementBlockNode_, cref<WienerFilter>>(m, "WienerFilterPtr")
+      .def(py::init([](py::object targetSignal, py::object noiseSignal, bool halfBandShift, float alpha, float flooringV, double beta, const std::string& nm) {
+             VectorComplexFeatureStreamPtr t = as_cstream(targetSignal), n = as_cstream(noiseSignal);
+             return new WienerFilter(t, n, halfBandShift, alpha, flooringV, beta, nm);
+           }), py::arg("targetSignal"), py::arg("noiseSignal"), py::arg("halfBandShift") = false, py::arg("alpha") = 0.0f,
+           py::arg("flooringV") = 0.001f, py::arg("beta") = 1.0, py::arg("nm") = "WienerFilter")
+      .def("set_noise_amplification_factor", &WienerFilter::set_noise_amplification_factor, py::arg("beta"))
+      .def("start_updating_noise_PSD", &WienerFilter::start_updating_noise_PSD)
+      .def("stop_updating_noise_PSD", &WienerFilter::stop_updating_noise_PSD)
+      .def("target_psd", [](WienerFilter& w) {
+             const std::vector<double> r = w.target_psd();
+             py::array_t<double> a((py::ssize_t)r.size());
+             memcpy(a.mutable_data(), r.data(), sizeof(double) * r.size());
+             return a;
+           })
+      .def("noise_psd", [](WienerFilter& w) {
+             const std::vector<double> r = w.noise_psd();
+             py::array_t<double> a((py::ssize_t)r.size());
+             memcpy(a.mutable_data(), r.data(), sizeof(double) * r.size());
+             return a;
+           });
+  // (cutOffFreq = 150 is the default of the reference's Python interface, postfilter/postfilter.i:298 -- the C++ constructor has
+  // none, postfilter.h:209 -- and, as there, it stands in front of a parameter without one: usable by keyword only)
+  py::class_<HighPassFilter, EnhancementBlockNode_, cref<HighPassFilter>>(m, "HighPassFilterPtr")
+      .def(py::init([](py::object output, float cutOffFreq, int sampleRate, const std::string& nm) {
+             VectorComplexFeatureStreamPtr p = as_cstream(output);
+             return new HighPassFilter(p, cutOffFreq, sampleRate, nm);
+           }), py::arg("output"), py::arg("cutOffFreq") = 150.0f, py::arg("sampleRate"), py::arg("nm") = "HighPassFilter")
+      .def("cutoff_bin", &HighPassFilter::cutoff_bin);
 }

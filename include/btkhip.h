@@ -770,6 +770,63 @@ int  btk_conv_apply(const float* x, long len, long hist, long x_stride, int S, c
 int  btk_conv_blocks(const float* x, long len, long x_stride, int S, long T, long block_step, const void* H, int S_h, int C, int P,
                      int L, float* y, void* stream);
 
+/* ---- Single-channel enhancement: spectral subtraction, Wiener filter, spectral high-pass (csrc/ss_kernels.hip) ----------------
+ * Replace SpectralSubtractor::next with AveragePSDEstimator::add_sample / average / clear / clear_samples
+ * (postfilter/spectralsubtraction.cc:216-285, :89-119, :70-87, :57-68, :121-129), WienerFilter::next (:314-362) and
+ * HighPassFilter::next (postfilter/postfilter.cc:1215-1239) over a block of T frames.
+ * Layouts [dev]: complex64, bins 0 .. M/2 (K = M/2 + 1), T valid frames in rows T_stride apart.  X [S][K][C][T_stride] (the
+ * snapshot layout with C = number of channels set), Sx, Nx, Y [S][K][T_stride]; bins above M/2 are the caller's mirror
+ * Y[M-m] = conj(Y[m]).  Memory between T and T_stride is neither read nor written.
+ * flags [dev] uint8 [T], shared by all streams: the mode of each frame, so that a block computed in one launch follows mode
+ * switches between two next() calls (or a VAD label).  NULL: every frame has `mode`.
+ *
+ * btk_ss_process: per (s, k, t) the channels c = 0 .. C-1 in order, p = |X|^2:
+ *   BTK_SS_TRAIN, alpha[c] >= 0 (recursive): the first training frame the channel sees since clear() sets est = p, later ones
+ *     est = alpha est + (1 - alpha) p -- BEFORE the frame is subtracted (add_sample precedes estimate(), :227-235)
+ *   BTK_SS_TRAIN, alpha[c] < 0 (averaging): acc += p (per bin); est moves in btk_ss_finish_training only
+ *   BTK_SS_SUBTRACT: term = X sqrt(S2)/|X|, S2 = max(p - ft est, flooringV) (:267-271; (sqrt(S2), 0) where X = 0, the polar form
+ *     with gsl_complex_arg(0) = 0); otherwise term = X
+ *   Y = (sum_c term)/C
+ *   State [dev], caller-owned, continued bit for bit from block to block: est, acc float64 [S][C][K]; count int64 [S][C]
+ *   (training frames summed into acc; averaging channels only); added uint8 [S][C] (sample_added_; recursive channels only).
+ *   alpha [host] float64 [C]; alpha, ft and flooringV are rounded to float32, which is what the reference's members hold.
+ *   frames_done = frames this node produced before the block: the 64-frame scan chunks of the
+ *   recursion sit on multiples of 64 of that counter, so blocks cut at such multiples give the bits of one launch.
+ *   Arithmetic: |X|^2, the scan inside a chunk and the subtraction are float32; the carry from chunk to chunk, the state and
+ *   the averaging sum (products and sum) are float64.
+ *   form: BTK_SS_FORM_AUTO picks the frame-parallel kernel (rows cut along T across workgroups) when no frame can train
+ *   (flags == NULL and mode without BTK_SS_TRAIN) and the one-wavefront-per-row scan kernel otherwise; BTK_SS_FORM_ROWS forces
+ *   the latter (same bits).
+ * btk_ss_finish_training = average() (:70-87): est = acc (1.0/(float)count) on averaging channels (count = 0: 0 x inf = NaN, as there).
+ * btk_ss_clear: what = 0 clear_noise_samples() (acc = 0, count = 0), what = 1 clear() (added = 0 as well); est stays in both.
+ * btk_wiener_process: bin 0 of Y is Sx's and its state is never touched; for k >= 1
+ *     PSDs = a PSDs + (1 - a)|S|^2;  BTK_WIENER_UPDATE_NOISE: PSDn = a PSDn + (1 - a) max(|N|^2, flooringV), else PSDn stays
+ *     H = PSDs/(PSDs + beta PSDn),  Y = H S      (0/0 stays NaN)
+ *   a = 0 for the stream's first two frames (frame_no_ > 0 is tested before the increment, :323-326), alpha afterwards;
+ *   frames_done as above.  State [dev] psd_s, psd_n float64 [S][K] (row 0 unused).  Nx may be NULL when flags == NULL and mode
+ *   has no BTK_WIENER_UPDATE_NOISE.
+ * btk_spec_highpass: bins 0 .. cutoff-1 of Y are zero (the reference never writes bin 0, so DC goes too), bins cutoff .. M/2 are
+ *   X's.  cutoff = (unsigned)(M cutOffFreq/(float)sampleRate) is the caller's; cutoff = 0, with which the reference writes
+ *   vector_[M] out of range, copies all K bins here.  X == Y is allowed.
+ * Limits: M even, 2 <= M <= 2048, 1 <= C <= btk_ss_max_channels() (64), 1 <= S <= 65535 (a grid dimension), 0 <= T <= T_stride, 0 <= cutoff <= M/2 + 1;
+ * BTK_ERR_DIMENSION beyond them, BTK_ERR_PARAMETER for a null pointer, an unknown mode bit, form or what; nothing is launched.   */
+#define BTK_SS_TRAIN 1
+#define BTK_SS_SUBTRACT 2
+#define BTK_WIENER_UPDATE_NOISE 1
+#define BTK_SS_FORM_AUTO 0
+#define BTK_SS_FORM_ROWS 1
+int  btk_ss_max_channels(void);
+int  btk_ss_process(const void* X, void* Y, int S, int M, int C, long T_stride, long T, const unsigned char* flags, int mode,
+                    double ft, double flooringV, const double* alpha, long frames_done, double* est, double* acc,
+                    long long* count, unsigned char* added, int form, void* stream);
+int  btk_ss_finish_training(int S, int M, int C, const double* alpha, double* est, const double* acc, const long long* count,
+                            void* stream);
+int  btk_ss_clear(int S, int M, int C, int what, double* acc, long long* count, unsigned char* added, void* stream);
+int  btk_wiener_process(const void* Sx, const void* Nx, void* Y, int S, int M, long T_stride, long T, const unsigned char* flags,
+                        int mode, double alpha, double flooringV, double beta, long frames_done, double* psd_s, double* psd_n,
+                        void* stream);
+int  btk_spec_highpass(const void* X, void* Y, int S, int M, int cutoff, long T_stride, long T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,8 @@ CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature"
            "McCowanPostFilter", "LefkimmiatisPostFilter", "MultiChannelWPEDereverberation", "MultiChannelWPEDereverberationFeature",
            "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream",
            "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature", "BlockKalmanFilterEchoCancellationFeature",
-           "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave"]
+           "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter",
+           "HighPassFilter"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
 
 
