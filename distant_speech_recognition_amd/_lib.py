@@ -177,6 +177,20 @@ SIGNATURES = {
     "btk_ss_clear": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "btk_wiener_process": (_i, [_vp, _vp, _vp, _i, _i, _l, _l, _vp, _i, _d, _d, _d, _l, _vp, _vp, _vp]),
     "btk_spec_highpass": (_i, [_vp, _vp, _i, _i, _i, _l, _l, _vp]),
+    # PR banks and the windowed FFT bank: PerfectReconstructionFFTAnalysisBank / ...SynthesisBank / NormalFFTAnalysisBank
+    # (modulated/modulated.cc:683-718, :861-898, :203-227) and get_window (:47-72)
+    "btk_get_window": (_i, [_i, _i, _vp]),
+    "btk_prfb_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _vp, _l]),
+    "btk_prfb_destroy": (None, [_vp]),
+    "btk_prfb_processing_delay": (_i, [_vp]),
+    "btk_prfb_num_frames": (_l, [_vp, _l]),
+    "btk_prfb_num_blocks": (_l, [_vp, _l]),
+    "btk_prfb_analysis": (_i, [_vp, _vp, _l, _l, _i, _i, _vp, _l, _l, _l, _vp]),
+    "btk_prfb_synthesis": (_i, [_vp, _vp, _l, _l, _i, _vp, _l, _l, _l, _vp]),
+    "btk_stft_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
+    "btk_stft_destroy": (None, [_vp]),
+    "btk_stft_num_frames": (_l, [_vp, _l]),
+    "btk_stft_analysis": (_i, [_vp, _vp, _l, _l, _i, _i, _vp, _l, _l, _l, _vp]),
 }
 
 

@@ -153,6 +153,9 @@ MelFeature, LogFeature, CepstralFeature = _mod.MelFeaturePtr, _mod.LogFeaturePtr
 StorageFeature = _mod.StorageFeaturePtr
 OverlapAdd, OverlapSave = _mod.OverlapAddPtr, _mod.OverlapSavePtr
 OverSampledDFTAnalysisBank, OverSampledDFTSynthesisBank = _mod.OverSampledDFTAnalysisBankPtr, _mod.OverSampledDFTSynthesisBankPtr
+NormalFFTAnalysisBank, DelayFeature = _mod.NormalFFTAnalysisBankPtr, _mod.DelayFeaturePtr
+PerfectReconstructionFFTAnalysisBank = _mod.PerfectReconstructionFFTAnalysisBankPtr
+PerfectReconstructionFFTSynthesisBank = _mod.PerfectReconstructionFFTSynthesisBankPtr
 SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _mod.SubbandGSCRLSPtr
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
 ZelinskiPostFilter, McCowanPostFilter, LefkimmiatisPostFilter = _mod.ZelinskiPostFilterPtr, _mod.McCowanPostFilterPtr, _mod.LefkimmiatisPostFilterPtr
@@ -168,4 +171,5 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter", "McCowanPostFilter", "LefkimmiatisPostFilter",
             "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
             "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
-            "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter", "HighPassFilter"]
+            "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter", "HighPassFilter",
+            "NormalFFTAnalysisBank", "DelayFeature", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank"]

@@ -49,6 +49,8 @@ CTOR_KWARGS = {
     # the class spells them cutOffFreq / sampleRate, the .i file cut_off_freq / samplerate (the generated table); these are the class's;
     # 150 is postfilter.i:298's default
     'HighPassFilterPtr': [('output', None), ('cutOffFreq', 150.0), ('sampleRate', None), ('nm', 'HighPassFilter')],
+    # the class spells it windowType (modulated.h:168), the .i file window_type (the generated table)
+    'NormalFFTAnalysisBankPtr': [('samp', None), ('fftLen', None), ('r', 1), ('windowType', 1), ('nm', 'NormalFFTAnalysisBank')],
     'OverlapAddPtr': [('samp', None), ('impulse_response', None), ('fft_len', 0), ('nm', 'Overlap Add')],
     'OverlapSavePtr': [('samp', None), ('impulse_response', None), ('nm', 'Overlap Save')],
     'LefkimmiatisPostFilterPtr': [('output', None), ('fftlen', None), ('min_sv', 1e-08), ('fbin_no1', 0), ('alpha', 0.6), ('type', 2), ('min_frames', 0), ('threshold', 0.99), ('nm', 'LefkimmiatisPostFilterPtr')],

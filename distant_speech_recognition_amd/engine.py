@@ -2126,3 +2126,93 @@ def conv_blocks(x, filt, L, block_step):
     check(_lib.lib().btk_conv_blocks(_ptr(x), n, stride, S, T, block_step, _ptr(filt.H), filt.S_h, filt.C, filt.P, L, _ptr(out),
                                      _stream()))
     return out
+
+
+# ---------------------------------------------------------------------------- PR banks and the windowed FFT bank (fb_pr_kernels.hip)
+def get_window(window_type, length):
+    """get_window (modulated.cc:47-72): 0 rectangular, 2 Hann, anything else Hamming -> float64 [length].  Host side."""
+    w = np.zeros(int(length), np.float64)
+    check(_lib.lib().btk_get_window(int(window_type), int(length), _np_ptr(w)))
+    return w
+
+
+class _FrameBank:
+    """What PRFilterBank and STFTBank share: a plan handle and the analysis launch over frames [t0, t0 + tcount)."""
+    _destroy = _frames = _analysis = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                getattr(_lib.lib(), self._destroy)(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def num_frames(self, nsamples):
+        return getattr(_lib.lib(), self._frames)(self._h, nsamples)
+
+    def analysis(self, pcm, nsamples=None, t0=0, tcount=None, out=None):
+        """pcm float32 [S][N][L] (cuda) -> X complex64 [S][bins][N][T], every bin of the transform; `out` may be a row-padded view."""
+        _check(pcm, "pcm", torch.float32, 3)
+        S, N, L = pcm.shape
+        nsamples = L if nsamples is None else nsamples
+        if tcount is None:
+            tcount = self.num_frames(nsamples) - t0
+        if out is None:
+            out = torch.empty((S, self.bins, N, tcount), dtype=torch.complex64, device=pcm.device)
+        ts = _check(out, "X", torch.complex64, (S, self.bins, N, None), rows=True)
+        if out.shape[3] < tcount:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "X holds %d frames, %d requested" % (out.shape[3], tcount))
+        check(getattr(_lib.lib(), self._analysis)(self._h, _ptr(pcm), nsamples, L, S, N, _ptr(out), ts, t0, tcount, _stream()))
+        return out
+
+
+class PRFilterBank(_FrameBank):
+    """Plan of a cosine-modulated perfect-reconstruction bank (PerfectReconstructionFilterBank, modulated.cc:284-300): 2 M complex
+    bins per frame, frame shift D = M / 2^r, prototype of length 2 M m."""
+    _destroy, _frames, _analysis = "btk_prfb_destroy", "btk_prfb_num_frames", "btk_prfb_analysis"
+
+    def __init__(self, prototype, M, m, r, synthesis=False):
+        proto = np.ascontiguousarray(prototype, np.float64).reshape(-1)
+        self.M, self.m, self.r = M, m, r
+        self.M2 = self.bins = 2 * M
+        self.R = 1 << r
+        self.D = M // self.R
+        self.is_synthesis = bool(synthesis)
+        self._h = C.c_void_p()
+        check(_lib.lib().btk_prfb_create(C.byref(self._h), M, m, r, int(synthesis), _np_ptr(proto), proto.size))
+        self.processing_delay = _lib.lib().btk_prfb_processing_delay(self._h)
+
+    def num_blocks(self, nframes):
+        return _lib.lib().btk_prfb_num_blocks(self._h, nframes)
+
+    def synthesis(self, Y, nframes=None, b0=0, bcount=None, out=None):
+        """Y complex64 [S][M2][T] (cuda) -> float32 [S][bcount*D], blocks [b0, b0 + bcount)."""
+        t_stride = _row_stride(Y, "Y")            # Y may be a [..., :T] view of a row-padded buffer
+        if Y.dtype != torch.complex64 or Y.dim() != 3 or Y.shape[1] != self.M2:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "Y must be complex64 [S][%d][T], got %s %s" % (self.M2, Y.dtype, tuple(Y.shape)))
+        S, _, T = Y.shape
+        nframes = T if nframes is None else nframes
+        if bcount is None:
+            bcount = self.num_blocks(nframes) - b0
+        if out is None:
+            out = torch.empty((S, bcount * self.D), dtype=torch.float32, device=Y.device)
+        _check(out, "out", torch.float32, (S, None))
+        check(_lib.lib().btk_prfb_synthesis(self._h, _ptr(Y), nframes, t_stride, S, _ptr(out), out.shape[1], b0, bcount, _stream()))
+        return out
+
+    synthesize = synthesis                        # FilterBank's name for the same launch
+
+
+class STFTBank(_FrameBank):
+    """Plan of the windowed short-time FFT (NormalFFTAnalysisBank, modulated.cc:96-132): M bins per frame, frame shift M / 2^r."""
+    _destroy, _frames, _analysis = "btk_stft_destroy", "btk_stft_num_frames", "btk_stft_analysis"
+
+    def __init__(self, M, r=1, window_type=1):
+        self.M = self.bins = M
+        self.r, self.window_type = r, window_type
+        self.R = 1 << r
+        self.D = M // self.R
+        self._h = C.c_void_p()
+        check(_lib.lib().btk_stft_create(C.byref(self._h), M, r, window_type))

@@ -167,3 +167,120 @@ class OverSampledDFTSynthesisBank : public VectorFloatFeatureStream {
   long prev_nblocks_;
 };
 typedef Inherit<OverSampledDFTSynthesisBank, VectorFloatFeatureStreamPtr> OverSampledDFTSynthesisBankPtr;
+
+// ---- the cosine-modulated perfect-reconstruction banks, the windowed FFT bank and DelayFeature (reference
+// modulated/modulated.h:155-260, :342-441, :443-470; src/prfb_nodes.cc over csrc/fb_pr_kernels.hip)
+class SampleFeature;
+
+// What the two analysis nodes share: a sliding window of input blocks on the host, one launch per round of up to block_frames()
+// frames (a SampleFeature source hands its blocks over in bulk; any other float source is pulled one block, one frame, at a
+// time), frames served from the round's download.  Every frame has the bits of one launch over the whole utterance.
+class BlockAnalysisBank : public VectorComplexFeatureStream {
+ public:
+  virtual ~BlockAnalysisBank() {}
+  virtual const gsl_vector_complex* next(int frame_no = -5);
+  virtual void reset();
+  void set_block_frames(long n) { block_frames_ = n < 0 ? 0 : n; }
+  long block_frames() const { return block_frames_; }
+  long launches() const { return launches_; }
+ protected:
+  // hist_blocks: input blocks a frame reads (its own included); pd: zero-padded frames after the last input block
+  BlockAnalysisBank(VectorFloatFeatureStreamPtr& samp, unsigned bins, unsigned D, unsigned hist_blocks, unsigned pd, const String& nm);
+  virtual int launch_(const float* dpcm, long nsamples, void* dX, long T_stride, long t0, long tcount, void* stream) = 0;
+  VectorFloatFeatureStreamPtr samp_;
+ private:
+  void fill_();
+  SampleFeature* sample_;
+  unsigned D_, hist_blocks_, pd_;
+  long block_frames_, launches_;
+  std::vector<float> win_;                              // samples of input blocks win_b0_ .. nblk_ - 1
+  long win_b0_, nblk_;
+  bool eos_;
+  long chunk_base_, chunk_len_;                         // the frames of the current round: complex64 [bins][chunk_len_] in hX_
+  PinnedBuffer hIn_, hX_;
+  DeviceBuffer dIn_, dX_;
+};
+
+class NormalFFTAnalysisBank : public BlockAnalysisBank {
+ public:
+  NormalFFTAnalysisBank(VectorFloatFeatureStreamPtr& samp, unsigned fftLen, unsigned r = 1, unsigned windowType = 1,
+                        const String& nm = "NormalFFTAnalysisBank");
+  ~NormalFFTAnalysisBank();
+  unsigned fftlen() const { return M_; }
+  unsigned fftLen() const { return fftlen(); }          // ENABLE_LEGACY_BTK_API alias
+ protected:
+  virtual int launch_(const float* dpcm, long nsamples, void* dX, long T_stride, long t0, long tcount, void* stream);
+ private:
+  unsigned M_, r_, window_type_;
+  btk_stft_t* plan_;                                    // made at the first launch: construction touches no device
+};
+typedef Inherit<NormalFFTAnalysisBank, VectorComplexFeatureStreamPtr> NormalFFTAnalysisBankPtr;
+
+class PerfectReconstructionFFTAnalysisBank : public BlockAnalysisBank {
+ public:
+  PerfectReconstructionFFTAnalysisBank(VectorFloatFeatureStreamPtr& samp, gsl_vector* prototype, unsigned M, unsigned m, unsigned r,
+                                       const String& nm = "PerfectReconstructionFFTAnalysisBank");
+  ~PerfectReconstructionFFTAnalysisBank();
+  double polyphase(unsigned m, unsigned n) const { return proto_[m + 2 * M_ * n]; }
+  unsigned fftLen() const { return 2 * M_; }            // ENABLE_LEGACY_BTK_API accessors, constants as in the reference (modulated.h:372-376)
+  unsigned nBlocks() const { return 4; }
+  unsigned subSampRate() const { return 2; }
+ protected:
+  virtual int launch_(const float* dpcm, long nsamples, void* dX, long T_stride, long t0, long tcount, void* stream);
+ private:
+  unsigned M_, m_, r_;
+  std::vector<double> proto_;
+  btk_prfb_t* plan_;
+};
+typedef Inherit<PerfectReconstructionFFTAnalysisBank, VectorComplexFeatureStreamPtr> PerfectReconstructionFFTAnalysisBankPtr;
+
+// Rounds of up to block_frames() input frames drained from the source through next(); the window keeps the 2R - 1 + q (m-1) + pd
+// frames the next round's first block reaches back to.  Every block has the bits of one launch over the whole stream.
+class PerfectReconstructionFFTSynthesisBank : public VectorFloatFeatureStream {
+ public:
+  PerfectReconstructionFFTSynthesisBank(VectorComplexFeatureStreamPtr& samp, gsl_vector* prototype, unsigned M, unsigned m,
+                                        unsigned r = 0, const String& nm = "PerfectReconstructionFFTSynthesisBank");
+  // source-less form (modulated.cc:793-821): the reference has no way to push frames into it; next() raises j_error
+  PerfectReconstructionFFTSynthesisBank(gsl_vector* prototype, unsigned M, unsigned m, unsigned r = 0,
+                                        const String& nm = "PerfectReconstructionFFTSynthesisBF");
+  ~PerfectReconstructionFFTSynthesisBank();
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset();
+  double polyphase(unsigned m, unsigned n) const { return proto_[m + 2 * M_ * n]; }
+  void set_block_frames(long n) { block_frames_ = n < 0 ? 0 : n; }
+  long block_frames() const { return block_frames_; }
+  long launches() const { return launches_; }
+ private:
+  void init_(gsl_vector* prototype);
+  void fill_();
+  VectorComplexFeatureStreamPtr samp_;
+  bool have_source_;
+  unsigned M_, m_, r_, D_;
+  std::vector<double> proto_;
+  btk_prfb_t* plan_;
+  long block_frames_, launches_;
+  std::vector<float> frames_;                           // input frames win_f0_ .. nframes_ - 1, complex64 [frame][M2]
+  long win_f0_, nframes_;
+  bool src_ended_;
+  long blk_base_, nblocks_;                             // the blocks of the current round: float32 [nblocks_][D] in hOut_
+  PinnedBuffer hY_, hOut_;
+  DeviceBuffer dY_, dOut_;
+};
+typedef Inherit<PerfectReconstructionFFTSynthesisBank, VectorFloatFeatureStreamPtr> PerfectReconstructionFFTSynthesisBankPtr;
+
+// y = polar(1, time_delay) x per frame, one phase for all bins, in complex128 on the host (modulated.cc:908-935)
+class DelayFeature : public VectorComplexFeatureStream {
+ public:
+  DelayFeature(const VectorComplexFeatureStreamPtr& samp, float time_delay = 0.0, const String& nm = "DelayFeature");
+  ~DelayFeature() {}
+  void set_time_delay(float time_delay) { time_delay_ = time_delay; }
+  virtual const gsl_vector_complex* next(int frame_no = -5);
+  virtual void reset();
+ private:
+  VectorComplexFeatureStreamPtr samp_;
+  float time_delay_;
+};
+typedef Inherit<DelayFeature, VectorComplexFeatureStreamPtr> DelayFeaturePtr;
+
+// get_window (modulated.cc:47-72): 0 rectangular, 2 Hann, anything else Hamming; the caller frees the vector
+gsl_vector* get_window(unsigned winType, unsigned winLen);

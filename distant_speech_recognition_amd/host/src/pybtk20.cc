@@ -515,6 +515,65 @@ PYBIND11_MODULE(_btk20cpp, m)
              if (n > 0) memcpy(a.mutable_data(), p, sizeof(float) * (size_t)n * b.size());
              return a;
            }, py::arg("max_blocks") = 0);
+  // the PR banks, the windowed FFT bank, DelayFeature and get_window (modulated/modulated.i:46-86, :194-305, :477-478);
+  // block_frames / set_block_frames / launches are the engine's additions
+  py::class_<NormalFFTAnalysisBank, VectorComplexFeatureStream, cref<NormalFFTAnalysisBank>>(m, "NormalFFTAnalysisBankPtr")
+      .def(py::init([](py::object samp, unsigned fftLen, unsigned r, unsigned window_type, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             return new NormalFFTAnalysisBank(sp, fftLen, r, window_type, nm);
+           }), py::arg("samp"), py::arg("fftLen"), py::arg("r") = 1, py::arg("window_type") = 1, py::arg("nm") = "NormalFFTAnalysisBank")
+      .def("fftlen", &NormalFFTAnalysisBank::fftlen)
+      .def("fftLen", &NormalFFTAnalysisBank::fftlen)
+      .def("set_block_frames", [](NormalFFTAnalysisBank& b, long n) { b.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](NormalFFTAnalysisBank& b) { return b.block_frames(); })
+      .def("launches", [](NormalFFTAnalysisBank& b) { return b.launches(); });
+  py::class_<PerfectReconstructionFFTAnalysisBank, VectorComplexFeatureStream, cref<PerfectReconstructionFFTAnalysisBank>>(m, "PerfectReconstructionFFTAnalysisBankPtr")
+      .def(py::init([](py::object samp, py::array_t<double, py::array::c_style | py::array::forcecast> prototype, unsigned M, unsigned mm,
+                       unsigned r, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(samp);
+             GslVec h(prototype);
+             return new PerfectReconstructionFFTAnalysisBank(sp, h.v, M, mm, r, nm);
+           }), py::arg("samp"), py::arg("prototype"), py::arg("M") = 256, py::arg("m") = 3, py::arg("r") = 0,
+           py::arg("nm") = "PerfectReconstructionFFTAnalysisBankFloat")
+      .def("polyphase", &PerfectReconstructionFFTAnalysisBank::polyphase, py::arg("m"), py::arg("n"))
+      .def("fftLen", &PerfectReconstructionFFTAnalysisBank::fftLen)
+      .def("nBlocks", &PerfectReconstructionFFTAnalysisBank::nBlocks)
+      .def("subSampRate", &PerfectReconstructionFFTAnalysisBank::subSampRate)
+      .def("set_block_frames", [](PerfectReconstructionFFTAnalysisBank& b, long n) { b.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](PerfectReconstructionFFTAnalysisBank& b) { return b.block_frames(); })
+      .def("launches", [](PerfectReconstructionFFTAnalysisBank& b) { return b.launches(); });
+  py::class_<PerfectReconstructionFFTSynthesisBank, VectorFloatFeatureStream, cref<PerfectReconstructionFFTSynthesisBank>>(m, "PerfectReconstructionFFTSynthesisBankPtr")
+      // source-less form (modulated/modulated.i:250-251), registered first so that a prototype array in the first position is not
+      // taken for a source object
+      .def(py::init([](py::array_t<double, py::array::c_style | py::array::forcecast> prototype, unsigned M, unsigned mm, unsigned r,
+                       const std::string& nm) {
+             GslVec g(prototype);
+             return new PerfectReconstructionFFTSynthesisBank(g.v, M, mm, r, nm);
+           }), py::arg("prototype"), py::arg("M"), py::arg("m"), py::arg("r") = 0, py::arg("nm") = "PerfectReconstructionFFTSynthesisBF")
+      .def(py::init([](py::object samp, py::array_t<double, py::array::c_style | py::array::forcecast> prototype, unsigned M, unsigned mm,
+                       unsigned r, const std::string& nm) {
+             VectorComplexFeatureStreamPtr sp = as_cstream(samp);
+             GslVec g(prototype);
+             return new PerfectReconstructionFFTSynthesisBank(sp, g.v, M, mm, r, nm);
+           }), py::arg("samp"), py::arg("prototype"), py::arg("M"), py::arg("m"), py::arg("r") = 0,
+           py::arg("nm") = "PerfectReconstructionFFTSynthesisBank")
+      .def("polyphase", &PerfectReconstructionFFTSynthesisBank::polyphase, py::arg("m"), py::arg("n"))
+      .def("set_block_frames", &PerfectReconstructionFFTSynthesisBank::set_block_frames, py::arg("n"))
+      .def("block_frames", &PerfectReconstructionFFTSynthesisBank::block_frames)
+      .def("launches", &PerfectReconstructionFFTSynthesisBank::launches);
+  py::class_<DelayFeature, VectorComplexFeatureStream, cref<DelayFeature>>(m, "DelayFeaturePtr")
+      .def(py::init([](py::object samp, float time_delay, const std::string& nm) {
+             VectorComplexFeatureStreamPtr sp = as_cstream(samp);
+             return new DelayFeature(sp, time_delay, nm);
+           }), py::arg("samp"), py::arg("time_delay") = 0.0f, py::arg("nm") = "DelayFeature")
+      .def("set_time_delay", [](DelayFeature& f, double time_delay) { f.set_time_delay((float)time_delay); }, py::arg("time_delay"));
+  m.def("get_window", [](unsigned winType, unsigned winLen) {
+          gsl_vector* w = get_window(winType, winLen);
+          py::array_t<double> a((py::ssize_t)w->size);
+          memcpy(a.mutable_data(), w->data, sizeof(double) * w->size);
+          gsl_vector_free(w);
+          return a;
+        }, py::arg("winType"), py::arg("winLen"));
 
   // ---- beamformer/beamformer.h
   py::class_<SnapShotArray, cref<SnapShotArray>>(m, "SnapShotArrayPtr")

@@ -827,6 +827,42 @@ int  btk_wiener_process(const void* Sx, const void* Nx, void* Y, int S, int M, l
                         void* stream);
 int  btk_spec_highpass(const void* X, void* Y, int S, int M, int cutoff, long T_stride, long T, void* stream);
 
+/* ---- Cosine-modulated perfect-reconstruction (PR) banks and the windowed FFT bank (csrc/fb_pr_kernels.hip) --------------------
+ * Replace PerfectReconstructionFFTAnalysisBank::next, PerfectReconstructionFFTSynthesisBank::next and NormalFFTAnalysisBank::next
+ * (modulated/modulated.cc:683-718, :861-898, :203-227) and get_window (:47-72).  M2 = 2 M, R = 2^r, D = M / R, q = r + 2:
+ *   analysis  frame t, newest sample n_t = (t + 1) D - 1:  p[i] = sum_{k<m} (-1)^k h[i + M2 k] x[n_t - q k D - i],
+ *             X_t[kappa] = 1/M2 sum_i p[i] e^{-j pi i/M2} e^{+j 2 pi kappa i/M2}, all M2 bins; ceil(nsamples / D) + 2 m - 1 frames
+ *   synthesis block b, newest frame f = b + 2 m - 1:  v_f[i] = Re(e^{+j pi i/M2} sum_kappa Y_f[kappa] e^{-j 2 pi kappa i/M2}),
+ *             s_b[i] = sum_{k<m} (-1)^{k+m-1} h[i + M2 (m-1-k)] v_{f - q k}[i],  out_b[D-1-d] = sum_{sx<2R} s_{b-(2R-1-sx)}[d + sx D] / R
+ *             (float32 running sum in this order); frames and blocks before 0 count as zero; nframes - (2 m - 1) blocks
+ *   STFT      X_t[kappa] = sum_{i<M} win[i] x[n_t - M + 1 + i] e^{-j 2 pi kappa i/M}, all M bins; ceil(nsamples / D) + 1 frames
+ * Layouts [dev]: pcm float32 [S*N][pcm_stride]; X complex64 [S][M2][N][T_stride] (STFT: [S][M][N][T_stride]), the snapshot
+ * layout with K = M2; Y complex64 [S][M2][T_stride]; out float32 [S][out_stride].  A launch covers frames [t0, t0 + tcount) or
+ * blocks [b0, b0 + bcount), written from column 0 / sample 0 of the output; any split gives the bits of one launch.
+ * prototype [host] float64 [prototype_len]: BTK_ERR_CONSISTENCY unless prototype_len == 2 M m.
+ * Limits: PR banks M a power of two in 8 .. 1024 (M2 = 16 .. 2048), 1 <= m <= 64 (m <= 8 compiled in, above that a run-time
+ * loop), r <= 2; STFT M a power of two in 8 .. 2048, M >> r >= 1: BTK_ERR_PARAMETER otherwise.  A launch whose tile does not
+ * fit 160 KB of LDS (M2 = 2048 with a long prototype) is refused with BTK_ERR_PARAMETER, bad sizes with BTK_ERR_DIMENSION;
+ * nothing is launched and the outputs stay untouched.
+ * btk_get_window [host]: type 0 rectangular, 2 Hann 0.5 (1 - cos(2 pi i/(len-1))), anything else Hamming 0.54 - 0.46 cos(...).  */
+typedef struct btk_prfb btk_prfb_t;
+typedef struct btk_stft btk_stft_t;
+int  btk_get_window(int type, int len, double* out);
+int  btk_prfb_create(btk_prfb_t** fb, int M, int m, int r, int synthesis, const double* prototype, long prototype_len);
+void btk_prfb_destroy(btk_prfb_t* fb);
+int  btk_prfb_processing_delay(const btk_prfb_t* fb);
+long btk_prfb_num_frames(const btk_prfb_t* fb, long nsamples);
+long btk_prfb_num_blocks(const btk_prfb_t* fb, long nframes);
+int  btk_prfb_analysis(const btk_prfb_t* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
+                       long T_stride, long t0, long tcount, void* stream);
+int  btk_prfb_synthesis(const btk_prfb_t* fb, const void* Y, long nframes, long T_stride, int S, float* out, long out_stride,
+                        long b0, long bcount, void* stream);
+int  btk_stft_create(btk_stft_t** fb, int M, int r, int window_type);
+void btk_stft_destroy(btk_stft_t* fb);
+long btk_stft_num_frames(const btk_stft_t* fb, long nsamples);
+int  btk_stft_analysis(const btk_stft_t* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
+                       long T_stride, long t0, long tcount, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature"
            "SingleChannelWPEDereverberationFeature", "PyVectorFloatFeatureStream", "PyVectorComplexFeatureStream",
            "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature", "BlockKalmanFilterEchoCancellationFeature",
            "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter",
-           "HighPassFilter"]
+           "HighPassFilter", "NormalFFTAnalysisBank", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank",
+           "DelayFeature"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
 
 
