@@ -35,6 +35,7 @@ BTK_PF_MCCOWAN_RULES = 0x10      # type bit of btk_zelinski_process (include/btk
 BTK_SS_TRAIN, BTK_SS_SUBTRACT = 1, 2     # frame flags / mode bits of btk_ss_process
 BTK_WIENER_UPDATE_NOISE = 1              # frame flag / mode bit of btk_wiener_process
 BTK_SS_FORM_AUTO, BTK_SS_FORM_ROWS = 0, 1
+BTK_BINAURAL_KIM, BTK_BINAURAL_IID, BTK_BINAURAL_FDIID = 0, 1, 2     # kind of the btk_binaural_* entry points
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
@@ -191,6 +192,13 @@ SIGNATURES = {
     "btk_stft_destroy": (None, [_vp]),
     "btk_stft_num_frames": (_l, [_vp, _l]),
     "btk_stft_analysis": (_i, [_vp, _vp, _l, _l, _i, _i, _vp, _l, _l, _l, _vp]),
+    # binaural binary-mask filters and threshold estimators (postfilter/binauralprocessing.cc)
+    "btk_binaural_max_candidates": (_i, []),
+    "btk_binaural_mask": (_i, [_vp, _vp, _vp, _i, _i, _l, _l, _i, _i, _d, _vp, _d, _d, _l, _vp, _vp]),
+    "btk_binaural_stats_scratch_bytes": (_l, [_i, _i, _l, _i]),
+    "btk_binaural_stats": (_i, [_vp, _vp, _i, _i, _l, _l, _i, _vp, _i, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "btk_binaural_candidates": (_i, [_d, _d, _d, _vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "btk_binaural_threshold": (_i, [_i, _i, _i, _i, _vp, _vp, C.c_longlong, _d, C.POINTER(_d), _vp, _vp]),
 }
 
 

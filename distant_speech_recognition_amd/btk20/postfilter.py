@@ -4,7 +4,13 @@ from ..btk20cpp import (  # noqa: F401
     TYPE_ZELINSKI1_REAL, TYPE_ZELINSKI1_ABS, TYPE_APAB, TYPE_ZELINSKI2, NO_USE_POST_FILTER, ZelinskiPostFilterPtr,
     ZelinskiPostFilter, McCowanPostFilterPtr, McCowanPostFilter, LefkimmiatisPostFilterPtr, LefkimmiatisPostFilter,
     SpectralSubtractorPtr, SpectralSubtractor, WienerFilterPtr, WienerFilter, HighPassFilterPtr, HighPassFilter,
+    BinaryMaskFilterPtr, BinaryMaskFilter, KimBinaryMaskFilterPtr, KimBinaryMaskFilter, KimITDThresholdEstimatorPtr,
+    KimITDThresholdEstimator, IIDBinaryMaskFilterPtr, IIDBinaryMaskFilter, IIDThresholdEstimatorPtr, IIDThresholdEstimator,
+    FDIIDThresholdEstimatorPtr, FDIIDThresholdEstimator,
 )
 
 __all__ = ['TYPE_ZELINSKI1_REAL', 'TYPE_ZELINSKI1_ABS', 'TYPE_APAB', 'TYPE_ZELINSKI2', 'NO_USE_POST_FILTER', 'ZelinskiPostFilterPtr', 'ZelinskiPostFilter', 'McCowanPostFilterPtr', 'McCowanPostFilter', 'LefkimmiatisPostFilterPtr', 'LefkimmiatisPostFilter',
-           'SpectralSubtractorPtr', 'SpectralSubtractor', 'WienerFilterPtr', 'WienerFilter', 'HighPassFilterPtr', 'HighPassFilter']
+           'SpectralSubtractorPtr', 'SpectralSubtractor', 'WienerFilterPtr', 'WienerFilter', 'HighPassFilterPtr', 'HighPassFilter',
+           'BinaryMaskFilterPtr', 'BinaryMaskFilter', 'KimBinaryMaskFilterPtr', 'KimBinaryMaskFilter', 'KimITDThresholdEstimatorPtr',
+           'KimITDThresholdEstimator', 'IIDBinaryMaskFilterPtr', 'IIDBinaryMaskFilter', 'IIDThresholdEstimatorPtr', 'IIDThresholdEstimator',
+           'FDIIDThresholdEstimatorPtr', 'FDIIDThresholdEstimator']

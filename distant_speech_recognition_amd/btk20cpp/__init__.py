@@ -160,6 +160,9 @@ SubbandDS, SubbandGSC, SubbandGSCRLS = _mod.SubbandDSPtr, _mod.SubbandGSCPtr, _m
 SubbandMVDR, SubbandMVDRGSC = _mod.SubbandMVDRPtr, _mod.SubbandMVDRGSCPtr
 ZelinskiPostFilter, McCowanPostFilter, LefkimmiatisPostFilter = _mod.ZelinskiPostFilterPtr, _mod.McCowanPostFilterPtr, _mod.LefkimmiatisPostFilterPtr
 SpectralSubtractor, WienerFilter, HighPassFilter = _mod.SpectralSubtractorPtr, _mod.WienerFilterPtr, _mod.HighPassFilterPtr
+BinaryMaskFilter, KimBinaryMaskFilter, IIDBinaryMaskFilter = _mod.BinaryMaskFilterPtr, _mod.KimBinaryMaskFilterPtr, _mod.IIDBinaryMaskFilterPtr
+KimITDThresholdEstimator, IIDThresholdEstimator = _mod.KimITDThresholdEstimatorPtr, _mod.IIDThresholdEstimatorPtr
+FDIIDThresholdEstimator = _mod.FDIIDThresholdEstimatorPtr
 DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA = _mod.DOAEstimatorSRPBasePtr, _mod.DOAEstimatorSRPDSBLAPtr
 NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature = _mod.NLMSAcousticEchoCancellationFeaturePtr, _mod.KalmanFilterEchoCancellationFeaturePtr
 BlockKalmanFilterEchoCancellationFeature = _mod.BlockKalmanFilterEchoCancellationFeaturePtr
@@ -172,4 +175,6 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "DOAEstimatorSRPBase", "DOAEstimatorSRPDSBLA", "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature",
             "BlockKalmanFilterEchoCancellationFeature", "DTDBlockKalmanFilterEchoCancellationFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
             "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter", "HighPassFilter",
-            "NormalFFTAnalysisBank", "DelayFeature", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank"]
+            "NormalFFTAnalysisBank", "DelayFeature", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank",
+            "BinaryMaskFilter", "KimBinaryMaskFilter", "IIDBinaryMaskFilter", "KimITDThresholdEstimator", "IIDThresholdEstimator",
+            "FDIIDThresholdEstimator"]

@@ -59,6 +59,9 @@ CTOR_KWARGS = {
     # unit_test/correlate.py still spells the sample source's keywords the legacy way
     'SampleFeaturePtr': [('fn', ''), ('blockLen', 320), ('shiftLen', 160), ('padZeros', False), ('nm', 'Sample')],
     'SnapShotArrayPtr': [('fftlen', None), ('chan_num', None)],
+    # the class spells them srcL / minThreshold / dEta / dPowerCoeff (binauralprocessing.h:176-178), the .i file src_left /
+    # min_threshold / deta / dpowercoeff (the generated table); 1/15.0 is the header's default
+    'FDIIDThresholdEstimatorPtr': [('srcL', None), ('srcR', None), ('M', None), ('minThreshold', 0.0), ('maxThreshold', 0.0), ('width', 1000.0), ('dEta', 0.01), ('dPowerCoeff', 1 / 15.0), ('nm', 'FDIIDThresholdEstimator')],
 }
 
 ALIASES = {

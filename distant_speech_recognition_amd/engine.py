@@ -1167,6 +1167,163 @@ def spec_highpass(X, cutoff_bin, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------- binaural binary masks and threshold estimators
+_BINAURAL_KINDS = {"kim": _lib.BTK_BINAURAL_KIM, "iid": _lib.BTK_BINAURAL_IID, "fdiid": _lib.BTK_BINAURAL_FDIID}
+_BINAURAL_NV = {_lib.BTK_BINAURAL_KIM: 5, _lib.BTK_BINAURAL_IID: 6, _lib.BTK_BINAURAL_FDIID: 3}
+
+
+def _binaural_kind(kind):
+    k = _BINAURAL_KINDS.get(kind.lower()) if isinstance(kind, str) else (int(kind) if int(kind) in _BINAURAL_NV else None)
+    if k is None:
+        raise ValueError("binaural kind %r: 'kim', 'iid' or 'fdiid'" % (kind,))
+    return k
+
+
+def _binaural_pair(XL, XR, who):
+    ts = _check(XL, "XL", torch.complex64, 3, rows=True)
+    S, K, T = XL.shape
+    if K < 2 or 2 * (K - 1) > 2048:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: %d bins, 2 .. 1025 (M <= 2048) are supported" % (who, K))
+    if _check(XR, "XR", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: XL and XR must share one row stride" % who)
+    return ts, S, K, T
+
+
+def binaural_mask_state(S, M, device="cuda"):
+    """prevMu_ of S binary-mask filters (BinaryMaskFilter's constructor, postfilter/binauralprocessing.cc:71-72): float32 [S][K] of
+    ones.  reset() of the filters leaves it as it is."""
+    return torch.ones((int(S), int(M) // 2 + 1), dtype=torch.float32, device=torch.device(device))
+
+
+def binaural_mask(XL, XR, kind, chan, threshold, alpha, eta, state=None, thresholds=None, frames_done=0, out=None):
+    """Binary mask over a block (KimBinaryMaskFilter::masking1 / IIDBinaryMaskFilter::masking1, :138-179, :441-485): XL, XR
+    complex64 [S][K][T] (rows may be padded) -> Y [S][K][T] = mu X with X = XR if chan else XL and
+    mu_t = alpha mu_{t-1} + (1 - alpha) b_t, b_t in {1, eta}; bin 0 is XL's.  kind 'kim': b_t = 1 where the interaural time delay
+    is <= threshold (chan 0; the opposite for chan 1); 'iid': b_t = eta where |X_T| <= |X_I| + threshold.  thresholds: float [K],
+    one per bin, for 'iid' (Kim ignores it, as the reference does).  state: binaural_mask_state(), updated in place (None: ones);
+    frames_done: frames the stream produced before this block, which places the 64-frame scan chunks."""
+    kd = _binaural_kind(kind)
+    if kd == _lib.BTK_BINAURAL_FDIID:
+        raise ValueError("binaural_mask: 'kim' or 'iid'")
+    ts, S, K, T = _binaural_pair(XL, XR, "binaural_mask")
+    if int(chan) not in (0, 1):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural_mask: chan=%r, 0 or 1" % (chan,))
+    if state is None:
+        state = binaural_mask_state(S, 2 * (K - 1), XL.device)
+    _check(state, "state", torch.float32, (S, K))
+    if thresholds is not None:
+        if not torch.is_tensor(thresholds):
+            thresholds = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float32)).to(XL.device)
+        _check(thresholds, "thresholds", torch.float32, (K,))
+    if out is None:
+        out = rows_like(XL, (S, K, T))
+    elif _check(out, "out", torch.complex64, (S, K, T), rows=True) != ts:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural_mask: out must share the row stride of XL")
+    check(_lib.lib().btk_binaural_mask(_ptr(XL), _ptr(XR), _ptr(out), S, 2 * (K - 1), ts, T, kd, int(chan), float(threshold),
+                                       None if thresholds is None else _ptr(thresholds), float(alpha), float(eta),
+                                       int(frames_done), _ptr(state), _stream()))
+    return out
+
+
+def binaural_candidates(min, max, width):
+    """The threshold candidates as the estimators walk them (`for(float t=min;t<=max;t+=width)`, :321) and the size nCand_ of their
+    arrays, (int)((max-min)/width + 1.5) (:270): (float32 array, nCand).  The walk can be shorter than nCand ((0, 2, 0.1): 20 and
+    21); one that is longer, with which the reference writes past its arrays, is cut at nCand."""
+    n_walk, n_cand = C.c_int(0), C.c_int(0)
+    L = _lib.lib()
+    check(L.btk_binaural_candidates(float(min), float(max), float(width), None, 0, C.byref(n_walk), C.byref(n_cand)))
+    out = np.zeros(n_walk.value, np.float32)
+    check(L.btk_binaural_candidates(float(min), float(max), float(width), _np_ptr(out), out.size, C.byref(n_walk), C.byref(n_cand)))
+    return out, n_cand.value
+
+
+class BinauralStatsState:
+    """Sums of S threshold estimators, float64: 'kim' [S][nCand][5] (sums of R_T R_I, R_T, R_I, R_T^2, R_I^2), 'iid' [S][nCand][6]
+    (Y1, Y2, Y4 of the target, then of the interferer), 'fdiid' [S][K][nCand][3] (Y4, mean, sigma); count int64 [S] frames."""
+
+    def __init__(self, kind, S, M, n_cand, device="cuda"):
+        self.kind, self.S, self.M, self.Kb, self.n_cand = _binaural_kind(kind), int(S), int(M), int(M) // 2 + 1, int(n_cand)
+        if self.S < 1 or self.M < 2 or self.M % 2 or self.M > 2048:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "BinauralStatsState: S=%d M=%d" % (S, M))
+        if not 1 <= self.n_cand <= _lib.lib().btk_binaural_max_candidates():
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "BinauralStatsState: %d candidates" % n_cand)
+        nv = _BINAURAL_NV[self.kind]
+        shape = (self.S, self.Kb, self.n_cand, nv) if self.kind == _lib.BTK_BINAURAL_FDIID else (self.S, self.n_cand, nv)
+        self.sums = torch.zeros(shape, dtype=torch.float64, device=torch.device(device))
+        self.count = torch.zeros((self.S,), dtype=torch.int64, device=torch.device(device))
+
+    def clear(self):
+        """reset() of the estimators (:409-426): the sums and the frame count go."""
+        self.sums.zero_()
+        self.count.zero_()
+
+
+def _binaural_cands(cands):
+    """(float32 walk, nCand) from binaural_candidates()'s pair or from a plain sequence (nCand = its length)."""
+    if isinstance(cands, tuple) and len(cands) == 2 and np.ndim(cands[0]) == 1:
+        walk, n_cand = np.ascontiguousarray(cands[0], dtype=np.float32), int(cands[1])
+    else:
+        walk = np.ascontiguousarray(cands, dtype=np.float32).reshape(-1)
+        n_cand = walk.size
+    if n_cand < 1 or walk.size > n_cand:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural: %d candidates for %d slots" % (walk.size, n_cand))
+    return walk, n_cand
+
+
+def binaural_stats(XL, XR, kind, cands, eta, power_coeff, fbin_min, fbin_max, state=None, per_frame=False):
+    """Adds the frames of a block to the sums of the threshold estimators (accumStats1 of KimITDThresholdEstimator,
+    IIDThresholdEstimator, FDIIDThresholdEstimator, :314-353, :548-603, :794-838): XL (target), XR (interferer) complex64
+    [S][K][T], rows may be padded.  cands: binaural_candidates()'s pair or a sequence of thresholds; bins [fbin_min, fbin_max)
+    ('fdiid': always 1 .. M/2).  Returns the state (a new one without `state`); with per_frame=True also the terms of every
+    (frame, candidate), float64 [S][T][nCand][2] = R_T, R_I ('kim') or [S][T][nCand][6] = the frame's Y1, Y2, Y4 of target and
+    interferer ('iid')."""
+    kd = _binaural_kind(kind)
+    ts, S, K, T = _binaural_pair(XL, XR, "binaural_stats")
+    M = 2 * (K - 1)
+    walk, n_cand = _binaural_cands(cands)
+    if state is None:
+        state = BinauralStatsState(kd, S, M, n_cand, XL.device)
+    if (state.kind, state.S, state.M, state.n_cand) != (kd, S, M, n_cand):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural_stats: the state is for kind %d, S=%d, M=%d, %d candidates"
+                            % (state.kind, state.S, state.M, state.n_cand))
+    if kd != _lib.BTK_BINAURAL_FDIID and not 0 <= int(fbin_min) <= int(fbin_max) <= K:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural_stats: bins [%d, %d) outside 0 .. %d" % (fbin_min, fbin_max, K))
+    L = _lib.lib()
+    pf = None
+    if per_frame:
+        if kd == _lib.BTK_BINAURAL_FDIID:
+            raise ValueError("binaural_stats: no per-frame terms for 'fdiid'")
+        pf = torch.zeros((S, T, n_cand, 2 if kd == _lib.BTK_BINAURAL_KIM else 6), dtype=torch.float64, device=XL.device)
+    dc = torch.from_numpy(walk if walk.size else np.zeros(1, np.float32)).to(XL.device)
+    nbytes = L.btk_binaural_stats_scratch_bytes(kd, S, T, n_cand)
+    scratch = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=XL.device)
+    check(L.btk_binaural_stats(_ptr(XL), _ptr(XR), S, M, ts, T, kd, _ptr(dc), walk.size, n_cand, float(eta), float(power_coeff),
+                               int(fbin_min), int(fbin_max), _ptr(state.sums), _ptr(state.count),
+                               None if pf is None else _ptr(pf), _ptr(scratch), scratch.numel() * 8, _stream()))
+    return (state, pf) if per_frame else state
+
+
+def binaural_threshold(kind, state, cands, stream=0, beta=3.0):
+    """calc_threshold of the three estimators (:382-407, :632-660, :867-898) on the sums of one stream: 'kim' minimises the absolute
+    correlation coefficient, 'iid' and 'fdiid' maximise the kurtosis-like cost with beta = 3; ties: the first candidate for 'kim'
+    and 'iid', the last for 'fdiid'.  Returns (threshold, cost [nCand]) or, for 'fdiid', (threshold, cost [K][nCand], per-bin
+    thresholds [K]).  The sums are left as they are."""
+    kd = _binaural_kind(kind)
+    walk, n_cand = _binaural_cands(cands)
+    if state.kind != kd or state.n_cand != n_cand:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "binaural_threshold: the state is for kind %d with %d candidates" % (state.kind, state.n_cand))
+    sums = np.ascontiguousarray(state.sums[int(stream)].cpu().numpy())
+    count = int(state.count[int(stream)].item())
+    fd = kd == _lib.BTK_BINAURAL_FDIID
+    cost = np.zeros((state.Kb, n_cand) if fd else (n_cand,), np.float64)
+    per_bin = np.zeros(state.Kb, np.float64)
+    thr = C.c_double(0.0)
+    w = walk if walk.size else np.zeros(1, np.float32)
+    check(_lib.lib().btk_binaural_threshold(kd, state.M, n_cand, walk.size, _np_ptr(w), _np_ptr(sums), count, float(beta),
+                                            C.byref(thr), _np_ptr(cost), _np_ptr(per_bin)))
+    return (thr.value, cost, per_bin) if fd else (thr.value, cost)
+
+
 # ---------------------------------------------------------------------------- covariance accumulation
 def frame_energy(X, M):
     _need_cuda(X, "X")

@@ -24,6 +24,7 @@
 #include "modulated/modulated.h"
 #include "postfilter/postfilter.h"
 #include "postfilter/spectralsubtraction.h"
+#include "postfilter/binauralprocessing.h"
 
 namespace py = pybind11;
 typedef std::complex<double> cd;
@@ -1002,4 +1003,96 @@ PYBIND11_MODULE(_btk20cpp, m)
              return new HighPassFilter(p, cutOffFreq, sampleRate, nm);
            }), py::arg("output"), py::arg("cutOffFreq") = 150.0f, py::arg("sampleRate"), py::arg("nm") = "HighPassFilter")
       .def("cutoff_bin", &HighPassFilter::cutoff_bin);
+
+  // ---- postfilter/binauralprocessing.h (keyword names: postfilter/postfilter.i:321-558).  dPowerCoeff defaults to the header's
+  // 1/15.0 (IIDThresholdEstimator: 0.5): the .i file's integer 1/15 is 0 and makes every cost constant.
+  auto dvec = [](const gsl_vector* v) -> py::object {
+    if (!v) return py::none();
+    py::array_t<double> a((py::ssize_t)v->size);
+    for (size_t i = 0; i < v->size; i++) a.mutable_data()[i] = gsl_vector_get(v, i);
+    return std::move(a);
+  };
+  py::class_<BinaryMaskFilter, EnhancementBlockNode_, cref<BinaryMaskFilter>>(m, "BinaryMaskFilterPtr")
+      .def(py::init([](unsigned chanX, py::object srcL, py::object srcR, unsigned M, float threshold, float alpha, float dEta, const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(srcL), r = as_cstream(srcR);
+             return new BinaryMaskFilter(chanX, l, r, M, threshold, alpha, dEta, nm);
+           }), py::arg("chanX"), py::arg("srcL"), py::arg("srcR"), py::arg("M"), py::arg("threshold"), py::arg("alpha"),
+           py::arg("dEta") = 0.01f, py::arg("nm") = "BinaryMaskFilter")
+      .def("set_threshold", &BinaryMaskFilter::set_threshold, py::arg("threshold"))
+      .def("setThreshold", &BinaryMaskFilter::set_threshold, py::arg("threshold"))
+      .def("set_thresholds", [](BinaryMaskFilter& f, const py::array_t<double, py::array::c_style | py::array::forcecast>& t) { GslVec v(t); f.set_thresholds(v.v); }, py::arg("thresholds"))
+      .def("setThresholds", [](BinaryMaskFilter& f, const py::array_t<double, py::array::c_style | py::array::forcecast>& t) { GslVec v(t); f.set_thresholds(v.v); }, py::arg("thresholds"))
+      .def("threshold", &BinaryMaskFilter::threshold)
+      .def("getThreshold", &BinaryMaskFilter::threshold)
+      .def("thresholds", [dvec](BinaryMaskFilter& f) { return dvec(f.thresholds()); })
+      .def("getThresholds", [dvec](BinaryMaskFilter& f) { return dvec(f.thresholds()); })
+      .def("prev_mu", [](BinaryMaskFilter& f) {
+             const std::vector<float> r = f.prev_mu();
+             py::array_t<float> a((py::ssize_t)r.size());
+             if (!r.empty()) memcpy(a.mutable_data(), r.data(), sizeof(float) * r.size());
+             return a;
+           })
+      .def("device_block", [](BinaryMaskFilter& f) { return block_of(f); });
+  py::class_<KimBinaryMaskFilter, BinaryMaskFilter, cref<KimBinaryMaskFilter>>(m, "KimBinaryMaskFilterPtr")
+      .def(py::init([](unsigned chanX, py::object srcL, py::object srcR, unsigned M, float threshold, float alpha, float dEta, float dPowerCoeff,
+                       const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(srcL), r = as_cstream(srcR);
+             return new KimBinaryMaskFilter(chanX, l, r, M, threshold, alpha, dEta, dPowerCoeff, nm);
+           }), py::arg("chanX"), py::arg("srcL"), py::arg("srcR"), py::arg("M"), py::arg("threshold"), py::arg("alpha"),
+           py::arg("dEta") = 0.01f, py::arg("dPowerCoeff") = (float)(1 / 15.0), py::arg("nm") = "KimBinaryMaskFilter");
+  py::class_<IIDBinaryMaskFilter, BinaryMaskFilter, cref<IIDBinaryMaskFilter>>(m, "IIDBinaryMaskFilterPtr")
+      .def(py::init([](unsigned chanX, py::object srcL, py::object srcR, unsigned M, float threshold, float alpha, float dEta, const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(srcL), r = as_cstream(srcR);
+             return new IIDBinaryMaskFilter(chanX, l, r, M, threshold, alpha, dEta, nm);
+           }), py::arg("chanX"), py::arg("srcL"), py::arg("srcR"), py::arg("M"), py::arg("threshold"), py::arg("alpha"),
+           py::arg("dEta") = 0.01f, py::arg("nm") = "IIDBinaryMaskFilter");
+  py::class_<KimITDThresholdEstimator, KimBinaryMaskFilter, cref<KimITDThresholdEstimator>>(m, "KimITDThresholdEstimatorPtr")
+      .def(py::init([](py::object srcL, py::object srcR, unsigned M, float minThreshold, float maxThreshold, float width, float minFreq, float maxFreq,
+                       int sampleRate, float dEta, float dPowerCoeff, const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(srcL), r = as_cstream(srcR);
+             return new KimITDThresholdEstimator(l, r, M, minThreshold, maxThreshold, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, nm);
+           }), py::arg("srcL"), py::arg("srcR"), py::arg("M"), py::arg("minThreshold") = 0.0f, py::arg("maxThreshold") = 0.0f,
+           py::arg("width") = 0.02f, py::arg("minFreq") = -1.0f, py::arg("maxFreq") = -1.0f, py::arg("sampleRate") = -1,
+           py::arg("dEta") = 0.01f, py::arg("dPowerCoeff") = (float)(1 / 15.0), py::arg("nm") = "KimITDThresholdEstimator")
+      .def("calc_threshold", &KimITDThresholdEstimator::calc_threshold)
+      .def("calcThreshold", &KimITDThresholdEstimator::calc_threshold)
+      .def("cost_function", [dvec](KimITDThresholdEstimator& e) { return dvec(e.cost_function()); })
+      .def("getCostFunction", [dvec](KimITDThresholdEstimator& e) { return dvec(e.cost_function()); })
+      .def("num_candidates", &KimITDThresholdEstimator::num_candidates)
+      .def("candidates", [](KimITDThresholdEstimator& e) {
+             const std::vector<float>& c = e.candidates();
+             py::array_t<float> a((py::ssize_t)c.size());
+             if (!c.empty()) memcpy(a.mutable_data(), c.data(), sizeof(float) * c.size());
+             return a;
+           })
+      .def("min_fbin", &KimITDThresholdEstimator::min_fbin)
+      .def("max_fbin", &KimITDThresholdEstimator::max_fbin)
+      .def("num_samples", &KimITDThresholdEstimator::num_samples);
+  py::class_<IIDThresholdEstimator, KimITDThresholdEstimator, cref<IIDThresholdEstimator>>(m, "IIDThresholdEstimatorPtr")
+      .def(py::init([](py::object srcL, py::object srcR, unsigned M, float minThreshold, float maxThreshold, float width, float minFreq, float maxFreq,
+                       int sampleRate, float dEta, float dPowerCoeff, const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(srcL), r = as_cstream(srcR);
+             return new IIDThresholdEstimator(l, r, M, minThreshold, maxThreshold, width, minFreq, maxFreq, sampleRate, dEta, dPowerCoeff, nm);
+           }), py::arg("srcL"), py::arg("srcR"), py::arg("M"), py::arg("minThreshold") = 0.0f, py::arg("maxThreshold") = 0.0f,
+           py::arg("width") = 0.02f, py::arg("minFreq") = -1.0f, py::arg("maxFreq") = -1.0f, py::arg("sampleRate") = -1,
+           py::arg("dEta") = 0.01f, py::arg("dPowerCoeff") = 0.5f, py::arg("nm") = "IIDThresholdEstimator");
+  py::class_<FDIIDThresholdEstimator, BinaryMaskFilter, cref<FDIIDThresholdEstimator>>(m, "FDIIDThresholdEstimatorPtr")
+      .def(py::init([](py::object src_left, py::object src_right, unsigned M, float min_threshold, float max_threshold, float width, float deta,
+                       float dpowercoeff, const std::string& nm) {
+             VectorComplexFeatureStreamPtr l = as_cstream(src_left), r = as_cstream(src_right);
+             return new FDIIDThresholdEstimator(l, r, M, min_threshold, max_threshold, width, deta, dpowercoeff, nm);
+           }), py::arg("src_left"), py::arg("src_right"), py::arg("M"), py::arg("min_threshold") = 0.0f, py::arg("max_threshold") = 0.0f,
+           py::arg("width") = 1000.0f, py::arg("deta") = 0.01f, py::arg("dpowercoeff") = (float)(1 / 15.0),
+           py::arg("nm") = "FDIIDThresholdEstimator")
+      .def("calc_threshold", &FDIIDThresholdEstimator::calc_threshold)
+      .def("calcThreshold", &FDIIDThresholdEstimator::calc_threshold)
+      .def("cost_function", [dvec](FDIIDThresholdEstimator& e, unsigned freqX) { return dvec(e.cost_function(freqX)); }, py::arg("freqX"))
+      .def("getCostFunction", [dvec](FDIIDThresholdEstimator& e, unsigned freqX) { return dvec(e.cost_function(freqX)); }, py::arg("freqX"))
+      .def("num_candidates", &FDIIDThresholdEstimator::num_candidates)
+      .def("candidates", [](FDIIDThresholdEstimator& e) {
+             const std::vector<float>& c = e.candidates();
+             py::array_t<float> a((py::ssize_t)c.size());
+             if (!c.empty()) memcpy(a.mutable_data(), c.data(), sizeof(float) * c.size());
+             return a;
+           });
 }

@@ -863,6 +863,65 @@ long btk_stft_num_frames(const btk_stft_t* fb, long nsamples);
 int  btk_stft_analysis(const btk_stft_t* fb, const float* pcm, long nsamples, long pcm_stride, int S, int N, void* X,
                        long T_stride, long t0, long tcount, void* stream);
 
+/* ---- Binaural binary-mask filters and threshold estimators (csrc/binaural_kernels.hip) -----------------------------------------
+ * Replace KimBinaryMaskFilter::masking1 / IIDBinaryMaskFilter::masking1 (postfilter/binauralprocessing.cc:138-179, :441-485, with
+ * calcITDf :17-38), the accumStats1 of KimITDThresholdEstimator, IIDThresholdEstimator and FDIIDThresholdEstimator (:314-353,
+ * :548-603, :794-838), their candidate walk and their calc_threshold (:382-407, :632-660, :867-898).
+ * Layouts [dev]: XL, XR, Y complex64 [S][K][T_stride], K = M/2 + 1, T valid frames per row; memory between T and T_stride is
+ * neither read nor written.  Bins above M/2 are the caller's mirror.
+ *
+ * btk_binaural_mask: bin 0 of Y is XL's whatever chanX is.  For k >= 1, X = chanX ? XR : XL and
+ *     mu_t = alpha mu_{t-1} + (1 - alpha) b_t,   Y_t = mu_t X_t,   b_t in {1, eta}
+ *   BTK_BINAURAL_KIM: ITD = min(|d|, |d - 2 pi|, |d + 2 pi|) / (2 pi k / M), d = arg XL - arg XR (arg 0 = 0);
+ *     b_t = 1 where (ITD <= threshold) == (chanX == 0).  `thresholds` is ignored, as in the reference.
+ *   BTK_BINAURAL_IID: X_T = X, X_I the other input; b_t = eta where |X_T| <= |X_I| + thr, thr = thresholds[k] (float32 [K] [dev])
+ *     if given, else threshold.
+ *   threshold, alpha, eta are rounded to float32 (the reference's members); (1 - alpha) and (1 - alpha) eta are float32.
+ *   prev_mu [dev] float32 [S][K]: prevMu_, the caller initialises it to 1; row 0 is never touched.  Phases, magnitudes and the
+ *   comparisons are float64; the recursion is a float32 scan in 64-frame chunks on multiples of 64 of frames_done (frames the
+ *   node produced before the block) with the float32 mask carried from chunk to chunk: blocks cut at such multiples give the
+ *   bits of one launch.
+ * btk_binaural_stats adds T frames to state [dev] float64 and T to count [dev] int64 [S].  cands [dev] float32 [nWalk]: the
+ *   candidates; state has nCand >= nWalk slots per stream (see btk_binaural_candidates), those beyond nWalk are not touched.
+ *   XL is the target's stream, XR the interferer's (chanX = 0 of the estimators).
+ *   KIM   state [S][nCand][5]: sum over frames of R_T R_I, R_T, R_I, R_T^2, R_I^2 with R = (sum_{k in [fbin_min, fbin_max)}
+ *         |mu X_k|^2)^power_coeff, (mu_T, mu_I) = (1, eta) where ITD_k <= cand, else (eta, 1).  Bin 0 has ITD x/0: never <=.
+ *   IID   state [S][nCand][6]: Y1_T, Y2_T, Y4_T, Y1_I, Y2_I, Y4_I, sums over frames and bins of y, y^2, y^4 with
+ *         y = |mu X_k|^(2 power_coeff), mu_T = eta where |XL| <= |XR| + cand, mu_I = eta where |XR| <= |XL| + cand, else 1.
+ *   FDIID state [S][K][nCand][3]: Y4, mean, sigma = sums over frames of y_T^4 + y_I^4, y_T + y_I, y_T^2 + y_I^2 per bin 1 .. M/2
+ *         (row 0 untouched; fbin_min / fbin_max are ignored).
+ *   per_frame [dev] float64 or NULL: KIM [S][T][nCand][2] = R_T, R_I; IID [S][T][nCand][6] = the frame's six sums (FDIID: must be
+ *   NULL).  scratch [dev]: btk_binaural_stats_scratch_bytes(kind, S, T, nCand) bytes (0 for FDIID), per-chunk partial sums that
+ *   a second launch adds up in chunk order.  No floating-point atomics: same inputs and same block cuts, same bits.
+ *   eta and power_coeff are rounded to float32 (the reference's members), everything else is float64.
+ * btk_binaural_candidates [host]: the walk `for (float t = min; t <= max; t += width)` into out (at most cap values; out may be
+ *   NULL), its length in *nWalk, and *nCand = (int)((max - min)/width + 1.5) (float32 quotient), the size of the reference's
+ *   arrays.  The two can differ ((0, 2, 0.1): 20 and 21).  A walk longer than nCand, which in the reference writes past its
+ *   arrays, is cut at nCand.
+ * btk_binaural_threshold [host]: calc_threshold on downloaded sums of ONE stream (state as above without [S]), count frames.
+ *   KIM minimises |rho|, the correlation coefficient of R_T and R_I, first minimum wins; cost[nCand] = E[R_T R_I] (what
+ *   cost_function() returns there).  IID maximises cost = E[Y4_T] + E[Y4_I] - beta (E[Y2_T] + E[Y2_I])^2 (sums over bins), first
+ *   maximum wins.  FDIID: cost [K][nCand] = E[Y4] - beta E[sigma]^2 per bin; thresholds [K] the per-bin maximiser and *threshold
+ *   the maximiser over all bins, LAST maximum wins (<=) in both; thresholds[0] = 0.  Slots beyond nWalk have cost 0 and are not
+ *   candidates.  Nothing is modified: calling it again gives the same answer (the reference divides its sums in place).
+ * Limits: M even, 2 <= M <= 2048, 1 <= S <= 65535, 0 <= T <= T_stride, 1 <= nCand <= btk_binaural_max_candidates() (4096),
+ * 0 <= fbin_min <= fbin_max <= M/2 + 1: BTK_ERR_DIMENSION beyond them; BTK_ERR_PARAMETER for a null pointer, an unknown kind or
+ * chanX, a short scratch; nothing is launched and the state stays untouched.   */
+#define BTK_BINAURAL_KIM 0
+#define BTK_BINAURAL_IID 1
+#define BTK_BINAURAL_FDIID 2
+int  btk_binaural_max_candidates(void);
+int  btk_binaural_mask(const void* XL, const void* XR, void* Y, int S, int M, long T_stride, long T, int kind, int chanX,
+                       double threshold, const float* thresholds, double alpha, double eta, long frames_done, float* prev_mu,
+                       void* stream);
+long btk_binaural_stats_scratch_bytes(int kind, int S, long T, int nCand);
+int  btk_binaural_stats(const void* XL, const void* XR, int S, int M, long T_stride, long T, int kind, const float* cands,
+                        int nWalk, int nCand, double eta, double power_coeff, int fbin_min, int fbin_max, double* state,
+                        long long* count, double* per_frame, void* scratch, long scratch_bytes, void* stream);
+int  btk_binaural_candidates(double min, double max, double width, float* out, int cap, int* nWalk, int* nCand);
+int  btk_binaural_threshold(int kind, int M, int nCand, int nWalk, const float* cands, const double* state, long long count,
+                            double beta, double* threshold, double* cost, double* thresholds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature"
            "NLMSAcousticEchoCancellationFeature", "KalmanFilterEchoCancellationFeature", "BlockKalmanFilterEchoCancellationFeature",
            "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter",
            "HighPassFilter", "NormalFFTAnalysisBank", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank",
-           "DelayFeature"]
+           "DelayFeature", "BinaryMaskFilter", "KimBinaryMaskFilter", "KimITDThresholdEstimator", "IIDBinaryMaskFilter",
+           "IIDThresholdEstimator", "FDIIDThresholdEstimator"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
 
 
