@@ -36,6 +36,8 @@ BTK_SS_TRAIN, BTK_SS_SUBTRACT = 1, 2     # frame flags / mode bits of btk_ss_pro
 BTK_WIENER_UPDATE_NOISE = 1              # frame flag / mode bit of btk_wiener_process
 BTK_SS_FORM_AUTO, BTK_SS_FORM_ROWS = 0, 1
 BTK_BINAURAL_KIM, BTK_BINAURAL_IID, BTK_BINAURAL_FDIID = 0, 1, 2     # kind of the btk_binaural_* entry points
+BTK_VAD_POWER, BTK_VAD_NORMALIZED, BTK_VAD_TSPS = 0, 1, 2             # kind of btk_vad_band_power
+BTK_VAD_RULE_SINGLE, BTK_VAD_RULE_MI, BTK_VAD_RULE_MULTISTAGE = 0, 1, 2     # rule of btk_vad_hangover
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 
@@ -199,6 +201,15 @@ SIGNATURES = {
     "btk_binaural_stats": (_i, [_vp, _vp, _i, _i, _l, _l, _i, _vp, _i, _i, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
     "btk_binaural_candidates": (_i, [_d, _d, _d, _vp, _i, C.POINTER(_i), C.POINTER(_i)]),
     "btk_binaural_threshold": (_i, [_i, _i, _i, _i, _vp, _vp, C.c_longlong, _d, C.POINTER(_d), _vp, _vp]),
+    # voice activity detection, the energy family of sad/sad.cc (:126-180, :472-836, :996-1063, :1712-1951)
+    "btk_vad_frame_energy": (_i, [_vp, _i, _i, _i, _l, _l, _l, _l, _vp, _l, _vp]),
+    "btk_vad_band_limits": (_i, [_i, _d, _d, _d, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "btk_vad_band_power": (_i, [_vp, _i, _i, _i, _i, _l, _l, _l, _l, _l, _i, _i, _d, _vp, _vp, _vp, _l, _vp]),
+    "btk_vad_energy_metric_state_bytes": (_l, [_i]),
+    "btk_vad_energy_metric": (_i, [_vp, _l, _i, _l, _i, _i, C.c_uint, C.c_uint, _vp, _vp, _l, _vp]),
+    "btk_vad_simple_energy": (_i, [_vp, _l, _i, _l, _d, _d, _vp, _vp, _vp, _l, _vp]),
+    "btk_vad_hangover": (_i, [_vp, _vp, _i, _i, _i, _l, _l, C.c_uint, C.c_uint, _i, _vp, _vp, _l, _vp, _i, _vp, _vp]),
+    "btk_vad_gather": (_i, [_vp, _i, _l, _i, _l, _vp, _vp, _l, _vp, _vp]),
 }
 
 

@@ -167,6 +167,12 @@ DOAEstimatorSRPBase, DOAEstimatorSRPDSBLA = _mod.DOAEstimatorSRPBasePtr, _mod.DO
 NLMSAcousticEchoCancellationFeature, KalmanFilterEchoCancellationFeature = _mod.NLMSAcousticEchoCancellationFeaturePtr, _mod.KalmanFilterEchoCancellationFeaturePtr
 BlockKalmanFilterEchoCancellationFeature = _mod.BlockKalmanFilterEchoCancellationFeaturePtr
 DTDBlockKalmanFilterEchoCancellationFeature = _mod.DTDBlockKalmanFilterEchoCancellationFeaturePtr
+SpectralPowerFloatFeature = _mod.SpectralPowerFloatFeaturePtr
+VADMetric, EnergyVADMetric, PowerSpectrumVADMetric = _mod.VADMetricPtr, _mod.EnergyVADMetricPtr, _mod.PowerSpectrumVADMetricPtr
+NormalizedEnergyMetric, TSPSVADMetric = _mod.NormalizedEnergyMetricPtr, _mod.TSPSVADMetricPtr
+VAD, SimpleEnergyVAD = _mod.VADPtr, _mod.SimpleEnergyVADPtr
+HangoverVADFeature, HangoverMIVADFeature = _mod.HangoverVADFeaturePtr, _mod.HangoverMIVADFeaturePtr
+HangoverMultiStageVADFeature = _mod.HangoverMultiStageVADFeaturePtr
 
 __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TYPE_APAB", "TYPE_ZELINSKI2", "NO_USE_POST_FILTER",
             "jarithmetic_error", "jinitialization_error", "jkey_error", "jparse_error", "jtype_error", "jiterator_error", "calc_all_delays",
@@ -177,4 +183,6 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "LogFeature", "CepstralFeature", "StorageFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter", "HighPassFilter",
             "NormalFFTAnalysisBank", "DelayFeature", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank",
             "BinaryMaskFilter", "KimBinaryMaskFilter", "IIDBinaryMaskFilter", "KimITDThresholdEstimator", "IIDThresholdEstimator",
-            "FDIIDThresholdEstimator"]
+            "FDIIDThresholdEstimator",
+            "SpectralPowerFloatFeature", "VADMetric", "EnergyVADMetric", "PowerSpectrumVADMetric", "NormalizedEnergyMetric", "TSPSVADMetric",
+            "VAD", "SimpleEnergyVAD", "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature"]

@@ -1324,6 +1324,244 @@ def binaural_threshold(kind, state, cands, stream=0, beta=3.0):
     return (thr.value, cost, per_bin) if fd else (thr.value, cost)
 
 
+# ---------------------------------------------------------------------------- voice activity detection (csrc/vad_kernels.hip)
+_VAD_KINDS = {"power": _lib.BTK_VAD_POWER, "normalized": _lib.BTK_VAD_NORMALIZED, "tsps": _lib.BTK_VAD_TSPS}
+_VAD_RULES = {"single": _lib.BTK_VAD_RULE_SINGLE, "mi": _lib.BTK_VAD_RULE_MI, "multistage": _lib.BTK_VAD_RULE_MULTISTAGE}
+_VAD_E0 = {_lib.BTK_VAD_POWER: 1.0, _lib.BTK_VAD_NORMALIZED: 1.0, _lib.BTK_VAD_TSPS: 5000.0}     # sad.cc:673, :767, :999
+
+
+def vad_frame_energy(x, frame_len=None, shift=None, layout=None):
+    """Frame energies sum_n |x[n]|^2, float64 in index order (EnergyVADMetric::above_threshold_, sad.cc:520-524; for complex input
+    re^2 + im^2 per element, SimpleEnergyVAD::next :165-167) -> float64 [S][T].  The blocks are read as their producers leave
+    them: layout 'rows' [S][D][T] (the snapshot layout, the default for complex64; rows may be padded), 'frames' [S][T][D] (the
+    default for float32), or PCM float32 [S][L] with frame_len and shift (T = (L - frame_len) // shift + 1 whole frames)."""
+    if x.dim() == 2:
+        _check(x, "x", torch.float32, 2)
+        if frame_len is None:
+            raise ValueError("vad_frame_energy: PCM needs frame_len")
+        S, L = x.shape
+        D, sh = int(frame_len), int(frame_len if shift is None else shift)
+        if D < 1 or sh < 1:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "vad_frame_energy: frame_len=%d shift=%d" % (D, sh))
+        T = (L - D) // sh + 1 if L >= D else 0
+        cplx, strides = 0, (L, sh, 1)
+    else:
+        cplx = 1 if x.dtype == torch.complex64 else 0
+        layout = layout or ("rows" if cplx else "frames")
+        if layout == "rows":
+            ts = _check(x, "x", x.dtype if cplx else torch.float32, 3, rows=True)
+            S, D, T = x.shape
+            strides = (D * ts, 1, ts)
+        elif layout == "frames":
+            _check(x, "x", x.dtype if cplx else torch.float32, 3)
+            S, T, D = x.shape
+            strides = (T * D, D, 1)
+        else:
+            raise ValueError("vad_frame_energy: layout %r: 'rows' or 'frames'" % (layout,))
+    e = torch.empty((S, T), dtype=torch.float64, device=x.device)
+    if T == 0:
+        return e
+    check(_lib.lib().btk_vad_frame_energy(_ptr(x), cplx, S, D, T, strides[0], strides[1], strides[2], _ptr(e), max(T, 1), _stream()))
+    return e
+
+
+def vad_band_limits(fftLen, samplerate, low_cutoff=-1.0, high_cutoff=-1.0):
+    """(lowX, highX, binN) of MultiChannelVADMetric (sad.cc:629-663); a cutoff >= samplerate / 2 raises BTK_ERR_DIMENSION."""
+    lo, hi, n = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(_lib.lib().btk_vad_band_limits(int(fftLen), float(samplerate), float(low_cutoff), float(high_cutoff), C.byref(lo),
+                                         C.byref(hi), C.byref(n)))
+    return lo.value, hi.value, n.value
+
+
+def vad_band_power(spec, kind, fftLen, lowX, highX, E0=None):
+    """Band powers and decisions of PowerSpectrumVADMetric / NormalizedEnergyMetric / TSPSVADMetric::next (sad.cc:694-739, :777-830,
+    :1005-1057): spec float32 [S][C][T][powN] power spectra, channel 0 the target's -> (P float64 [S][C][T], score float64 [S][T],
+    value float64 [S][T] = +-1).  kind 'power', 'normalized' or 'tsps'; E0 defaults to the reference's 1, 1, 5000."""
+    kd = _VAD_KINDS.get(kind) if isinstance(kind, str) else int(kind)
+    if kd not in _VAD_E0:
+        raise ValueError("vad_band_power: kind %r: 'power', 'normalized' or 'tsps'" % (kind,))
+    _check(spec, "spec", torch.float32, 4)
+    S, Cn, T, powN = spec.shape
+    if int(highX) >= powN:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "vad_band_power: bin %d of spectra of %d values" % (highX, powN))
+    P = torch.empty((S, Cn, T), dtype=torch.float64, device=spec.device)
+    score = torch.empty((S, T), dtype=torch.float64, device=spec.device)
+    value = torch.empty((S, T), dtype=torch.float64, device=spec.device)
+    if T == 0:
+        return P, score, value
+    check(_lib.lib().btk_vad_band_power(_ptr(spec), kd, S, Cn, int(fftLen), T, Cn * T * powN, T * powN, powN, 1, int(lowX),
+                                        int(highX), float(_VAD_E0[kd] if E0 is None else E0), _ptr(P), _ptr(score), _ptr(value),
+                                        max(T, 1), _stream()))
+    return P, score, value
+
+
+class EnergyVADState:
+    """State of S EnergyVADMetric (sad.cc:472-506): int64 [S][4 + energiesN] = {ring position, recognizing, abovethresholdN,
+    belowThresholdN}, then the float64 window of the last energiesN energies as a ring, filled with initialEnergy."""
+
+    def __init__(self, S, energiesN, initial_energy, device="cuda"):
+        self.S, self.energiesN, self.initial_energy = int(S), int(energiesN), float(initial_energy)
+        if self.S < 1 or _lib.lib().btk_vad_energy_metric_state_bytes(self.energiesN) < 0:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "EnergyVADState: S=%d energiesN=%d (1 .. 1024)" % (S, energiesN))
+        self.buf = torch.zeros((self.S, 4 + self.energiesN), dtype=torch.int64, device=torch.device(device))
+        self.next_speaker()
+
+    def reset(self):
+        """EnergyVADMetric::reset (:493-497): the counters go, the window stays."""
+        self.buf[:, 1:4] = 0
+
+    def next_speaker(self):
+        """EnergyVADMetric::next_speaker (:499-506): the counters go and the window is initialEnergy again."""
+        self.buf[:, :4] = 0
+        self.buf[:, 4:] = torch.tensor([self.initial_energy], dtype=torch.float64).view(torch.int64).item()
+
+    def window(self):
+        """The windows, oldest energy first: float64 numpy [S][energiesN]."""
+        b = self.buf.cpu()
+        ring = b[:, 4:].contiguous().view(torch.float64).numpy()
+        return np.stack([np.roll(ring[s], -int(b[s, 0])) for s in range(self.S)])
+
+    def energy_percentile(self, percentile, s=0):
+        """EnergyVADMetric::energy_percentile (:544-553), the division by energiesN included."""
+        if percentile < 0.0 or percentile > 100.0:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "Percentile %g is out of range [0.0, 100.0]." % percentile)
+        x = int((percentile / 100.0) * self.energiesN)
+        if x >= self.energiesN:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "Percentile %g reads past the window" % percentile)
+        return float(np.sort(self.window()[s])[x]) / self.energiesN
+
+
+def vad_median_index(threshold, energiesN):
+    """medianX_ = unsigned(threshold energiesN) (sad.cc:477); an index outside the window (threshold >= 1, where the reference
+    reads past its array, or a negative threshold) raises BTK_ERR_DIMENSION."""
+    v = float(threshold) * int(energiesN)
+    if not (0.0 <= v) or int(v) >= int(energiesN):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "EnergyVADMetric: threshold %g puts the median index outside 0 .. %d"
+                            % (threshold, int(energiesN) - 1))
+    return int(v)
+
+
+def vad_energy_metric(energy, state, threshold, headN, tailN):
+    """EnergyVADMetric::next over a block (sad.cc:518-588): energy float64 [S][T] -> float64 [S][T] of 1.0 / 0.0; state (an
+    EnergyVADState) is carried on, so blocks cut anywhere give the bits of one call."""
+    _check(energy, "energy", torch.float64, (state.S, None))
+    S, T = energy.shape
+    mx = vad_median_index(threshold, state.energiesN)
+    value = torch.empty((S, T), dtype=torch.float64, device=energy.device)
+    if T == 0:
+        return value
+    check(_lib.lib().btk_vad_energy_metric(_ptr(energy), max(T, 1), S, T, state.energiesN, mx, int(headN), int(tailN),
+                                           _ptr(state.buf), _ptr(value), max(T, 1), _stream()))
+    return value
+
+
+class SimpleEnergyVADState:
+    """spectral_energy_ of S SimpleEnergyVAD (sad.cc:140-152): float64 [S], 0 at the start and after next_speaker()."""
+
+    def __init__(self, S, device="cuda"):
+        self.S = int(S)
+        self.s = torch.zeros((self.S,), dtype=torch.float64, device=torch.device(device))
+
+    def next_speaker(self):
+        self.s.zero_()
+
+
+def vad_simple_energy(energy, state, threshold, gamma):
+    """SimpleEnergyVAD::next over a block (sad.cc:165-171): energy float64 [S][T] (vad_frame_energy of the complex frames) ->
+    (is_speech int32 [S][T], smoothed float64 [S][T]); s <- gamma s + (1 - gamma) E, is_speech = E / s > threshold."""
+    _check(energy, "energy", torch.float64, (state.S, None))
+    S, T = energy.shape
+    sp = torch.empty((S, T), dtype=torch.int32, device=energy.device)
+    sm = torch.empty((S, T), dtype=torch.float64, device=energy.device)
+    if T == 0:
+        return sp, sm
+    check(_lib.lib().btk_vad_simple_energy(_ptr(energy), max(T, 1), S, T, float(gamma), float(threshold), _ptr(state.s), _ptr(sp),
+                                           _ptr(sm), max(T, 1), _stream()))
+    return sp, sm
+
+
+class HangoverState:
+    """State of S hangover machines (HangoverVADFeature, sad.cc:1712-1761): int64 [S][8] = {abovethresholdN, belowThresholdN,
+    recognizing, frames seen, start, end, ended, decision_metric}; start / end are -1 until they are known."""
+
+    def __init__(self, S, device="cuda"):
+        self.S = int(S)
+        self.buf = torch.empty((self.S, 8), dtype=torch.int64, device=torch.device(device))
+        self.reset()
+
+    def reset(self):
+        self.buf[:] = torch.tensor([0, 0, 0, 0, -1, -1, 0, 0], dtype=torch.int64)
+
+    def host(self):
+        """Downloaded: a list of dicts with start (prefixN()), end, ended, recognizing, frames, decision_metric per stream."""
+        b = self.buf.cpu().numpy()
+        return [dict(start=int(r[4]), end=int(r[5]), ended=bool(r[6]), recognizing=bool(r[2]), frames=int(r[3]),
+                     decision_metric=int(r[7])) for r in b]
+
+
+def vad_hangover(values, thresholds, rule, headN, tailN, state, restart=False):
+    """The detection rule and head/tail machine of HangoverVADFeature / HangoverMIVADFeature / HangoverMultiStageVADFeature
+    (sad.cc:1763-1843, :1859-1885, :1910-1951) over a block: values a list of up to 8 float64 [S][T] metric rows (or one tensor
+    [R][S][T]), thresholds one per row, rule 'single', 'mi' or 'multistage'.  Returns (decision int32 [S][T], segments int64
+    [S][n][2], nseg int32 [S]): the decision_metric() code after each frame and the (start, end) pairs completed in this block;
+    the segment found so far is in state.host().  restart: go on after an end and yield every segment."""
+    rl = _VAD_RULES.get(rule) if isinstance(rule, str) else int(rule)
+    if rl not in (0, 1, 2):
+        raise ValueError("vad_hangover: rule %r: 'single', 'mi' or 'multistage'" % (rule,))
+    rows = [values[i] for i in range(len(values))]
+    R = len(rows)
+    if not 1 <= R <= 8 or len(thresholds) != R:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "vad_hangover: %d metric rows (1 .. 8), %d thresholds" % (R, len(thresholds)))
+    for i, v in enumerate(rows):
+        _check(v, "values[%d]" % i, torch.float64, (state.S, rows[0].shape[-1]))
+    S, T = rows[0].shape
+    if int(headN) < 1 or int(tailN) < 0:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "vad_hangover: headN=%d (>= 1; the reference divides by it), tailN=%d" % (headN, tailN))
+    dev = rows[0].device
+    max_seg = T // 2 + 1
+    decision = torch.empty((S, T), dtype=torch.int32, device=dev)
+    segments = torch.full((S, max_seg, 2), -1, dtype=torch.int64, device=dev)
+    nseg = torch.zeros((S,), dtype=torch.int32, device=dev)
+    if T == 0:
+        return decision, segments, nseg
+    ptrs = (C.c_void_p * R)(*[v.data_ptr() for v in rows])
+    thr = (C.c_double * R)(*[float(t) for t in thresholds])
+    check(_lib.lib().btk_vad_hangover(ptrs, thr, R, rl, S, T, max(T, 1), int(headN), int(tailN), 1 if restart else 0,
+                                      _ptr(state.buf), _ptr(decision), max(T, 1), _ptr(segments), max_seg, _ptr(nseg), _stream()))
+    return decision, segments, nseg
+
+
+def vad_gather(src, state, frame_base=0, out=None, dst_rows=None):
+    """Source rows [start, end) of the hangover state's segment that lie in src float32 [S][T][D] (row 0 is frame frame_base) ->
+    (out float32 [S][dst_rows][D] with the rows at (frame - start), count int64 [S] rows copied by this call)."""
+    _check(src, "src", torch.float32, (state.S, None, None))
+    S, T, D = src.shape
+    if out is None:
+        out = torch.zeros((S, int(T if dst_rows is None else dst_rows), D), dtype=torch.float32, device=src.device)
+    _check(out, "out", torch.float32, (S, None, D))
+    count = torch.zeros((S,), dtype=torch.int64, device=src.device)
+    if T == 0 or out.shape[1] == 0:
+        return out, count
+    check(_lib.lib().btk_vad_gather(_ptr(src), S, T, D, int(frame_base), _ptr(state.buf), _ptr(out), out.shape[1], _ptr(count),
+                                    _stream()))
+    return out, count
+
+
+def vad_segments_to_labels(segments, shiftlen, samplerate):
+    """Frame segments [(start, end), ...] (end exclusive, ascending, as vad_hangover yields them) as the `vad_label` list
+    [[start_s, end_s], ...] that accu_stats_from_label walks (lib/pybeamformer.py:967-985): that loop adds shiftlen / samplerate
+    frame by frame and takes a frame as target where start_s <= elapsed <= end_s, so the times are the loop's own sums at frames
+    start and end - 1 -- a frame is a target exactly when it lies in a segment."""
+    segs = [(int(a), int(b)) for a, b in segments if int(b) > int(a)]
+    if not segs:
+        return []
+    time_delta = int(shiftlen) / float(samplerate)
+    elapsed = np.zeros(max(b for _, b in segs), np.float64)
+    for t in range(1, elapsed.size):
+        elapsed[t] = elapsed[t - 1] + time_delta
+    return [[float(elapsed[a]), float(elapsed[b - 1])] for a, b in segs]
+
+
 # ---------------------------------------------------------------------------- covariance accumulation
 def frame_energy(X, M):
     _need_cuda(X, "X")

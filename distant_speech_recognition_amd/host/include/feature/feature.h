@@ -256,6 +256,19 @@ class SpectralPowerFeature : public VectorFeatureStream, public FeStageNode {
 };
 typedef Inherit<SpectralPowerFeature, VectorFeatureStreamPtr> SpectralPowerFeaturePtr;
 
+// SpectralPowerFloatFeature (reference feature/feature.h:557-571, feature/feature.cc:1263-1286): |X_k|^2 as float32 -- re^2 + im^2
+// summed in float64, rounded once -- for powN = fft->size() or fft->size() / 2 + 1 bins; the reference's only float stream of
+// power spectra and so the source of the band-power VAD metrics (sad/sad.h).  Host arithmetic: it is a node boundary.
+class SpectralPowerFloatFeature : public VectorFloatFeatureStream {
+ public:
+  SpectralPowerFloatFeature(const VectorComplexFeatureStreamPtr& fft, unsigned powN = 0, const String& nm = "Power");   // the name feature.i gives it
+  virtual const gsl_vector_float* next(int frame_no = -5);
+  virtual void reset() { fft_->reset(); VectorFloatFeatureStream::reset(); }
+ private:
+  VectorComplexFeatureStreamPtr fft_;
+};
+typedef Inherit<SpectralPowerFloatFeature, VectorFloatFeatureStreamPtr> SpectralPowerFloatFeaturePtr;
+
 class VTLNFeature : public VectorFeatureStream, public FeStageNode {
  public:
   VTLNFeature(const VectorFeatureStreamPtr& pow, unsigned coeffN = 0, double ratio = 1.0, double edge = 1.0, int version = 1,

@@ -387,6 +387,27 @@ void SpectralPowerFeature::fe_pull_one(std::vector<float>& in, int& in_stage, in
   in_dim = 0;
 }
 
+// ================================================================================ SpectralPowerFloatFeature (feature.cc:1263-1286)
+SpectralPowerFloatFeature::SpectralPowerFloatFeature(const VectorComplexFeatureStreamPtr& fft, unsigned powN, const String& nm)
+    : VectorFloatFeatureStream(powN == 0 ? fft->size() : powN, nm), fft_(fft)
+{
+  if (size() != fft->size() && size() != (fft->size() / 2) + 1)
+    throw jconsistency_error("Number of power coefficients %d does not match FFT length %d.", size(), fft->size());
+}
+
+const gsl_vector_float* SpectralPowerFloatFeature::next(int frame_no)
+{
+  if (frame_no == frame_no_) return vector_;
+  check_frame_no(frame_no, frame_no_, name());
+  const gsl_vector_complex* X = fft_->next(frame_no_ + 1);
+  increment_();
+  for (unsigned i = 0; i < size(); i++) {
+    const double re = X->data[2 * i], im = X->data[2 * i + 1];
+    vector_->data[i] = (float)(re * re + im * im);
+  }
+  return vector_;
+}
+
 // ================================================================================ VTLNFeature (feature.cc:1662-1850)
 VTLNFeature::VTLNFeature(const VectorFeatureStreamPtr& pow, unsigned coeffN, double ratio, double edge, int version, const String& nm)
     : VectorFeatureStream(coeffN == 0 ? pow->size() : coeffN, nm), FeStageNode(BTK_FE_VTLN), pow_(pow), ratio_(ratio), edge_(edge),

@@ -1,6 +1,6 @@
 // pybtk20.cc -- Python binding of the C++ node layer (libbtk20hip.so): the classes the reference exposes through SWIG
 // (stream/stream.i, feature/feature.i, modulated/modulated.i, beamformer/beamformer.i, postfilter/postfilter.i,
-// dereverberation/dereverberation.i, convolution/convolution.i) bound with pybind11 under the same names.
+// dereverberation/dereverberation.i, convolution/convolution.i, sad/sad.i) bound with pybind11 under the same names.
 //   * a bound object IS the C++ node: the holder shares Countable's intrusive count with the refcountable_ptrs the nodes keep
 //     of each other, so Python and C++ references are one population;
 //   * next() returns a numpy VIEW of the node's vector_ (no copy; the array keeps the node alive) -- the reference's typemap
@@ -25,6 +25,7 @@
 #include "postfilter/postfilter.h"
 #include "postfilter/spectralsubtraction.h"
 #include "postfilter/binauralprocessing.h"
+#include "sad/sad.h"
 
 namespace py = pybind11;
 typedef std::complex<double> cd;
@@ -402,6 +403,11 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("set_block_frames", [](SpectralPowerFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
       .def("block_frames", [](SpectralPowerFeature& f) { return f.block_frames(); })
       .def("launches", [](SpectralPowerFeature& f) { return f.launches(); });
+  py::class_<SpectralPowerFloatFeature, VectorFloatFeatureStream, cref<SpectralPowerFloatFeature>>(m, "SpectralPowerFloatFeaturePtr")
+      .def(py::init([](py::object fft, unsigned powN, const std::string& nm) {
+             VectorComplexFeatureStreamPtr sp = as_cstream(fft);
+             return new SpectralPowerFloatFeature(sp, powN, nm);
+           }), py::arg("fft"), py::arg("powN") = 0, py::arg("nm") = "Power");
   py::class_<VTLNFeature, VectorFeatureStream, cref<VTLNFeature>>(m, "VTLNFeaturePtr")
       .def(py::init([](py::object pow, unsigned coeff_num, double ratio, double edge, int version, const std::string& nm) {
              VectorFeatureStreamPtr sp = as_dstream(pow);
@@ -1095,4 +1101,121 @@ PYBIND11_MODULE(_btk20cpp, m)
              if (!c.empty()) memcpy(a.mutable_data(), c.data(), sizeof(float) * c.size());
              return a;
            });
+
+  // ---- sad/sad.h (sad/sad.i): the energy family of the voice activity detection.  A metric is any bound VADMetric.
+  auto as_metric = [](const py::object& o) {
+    if (!py::isinstance<VADMetric>(o)) throw jparameter_error("expected a VAD metric (VADMetricPtr)");
+    return VADMetricPtr(o.cast<VADMetric*>());
+  };
+  py::class_<VADMetric, cref<VADMetric>>(m, "VADMetricPtr")
+      .def("next", [](VADMetric& v, int frame_no) { return v.next(frame_no); }, py::arg("frame_no") = -5)
+      .def("__next__", [](VADMetric& v) { return v.next(-5); })
+      .def("__iter__", [](py::object self) { self.attr("reset")(); return self; })
+      .def("reset", [](VADMetric& v) { v.reset(); })
+      .def("score", [](VADMetric& v) { return v.score(); })
+      .def("next_speaker", [](VADMetric& v) { v.next_speaker(); })
+      .def("nextSpeaker", [](VADMetric& v) { v.next_speaker(); })
+      .def("frame_no", [](VADMetric& v) { return v.frame_no(); })
+      .def("set_block_frames", [](VADMetric& v, long n) { v.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](VADMetric& v) { return v.block_frames(); })
+      .def("launches", [](VADMetric& v) { return v.launches(); });
+  py::class_<EnergyVADMetric, VADMetric, cref<EnergyVADMetric>>(m, "EnergyVADMetricPtr")
+      .def(py::init([](py::object source, double initialEnergy, double threshold, unsigned headN, unsigned tailN, unsigned energiesN,
+                       const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(source);
+             return new EnergyVADMetric(sp, initialEnergy, threshold, headN, tailN, energiesN, nm);
+           }), py::arg("source"), py::arg("initialEnergy") = 5.0e+07, py::arg("threshold") = 0.5, py::arg("headN") = 4, py::arg("tailN") = 10,
+           py::arg("energiesN") = 200, py::arg("nm") = "Energy VAD Metric")
+      .def("energy_percentile", &EnergyVADMetric::energy_percentile, py::arg("percentile") = 50.0)
+      .def("energyPercentile", &EnergyVADMetric::energy_percentile, py::arg("percentile") = 50.0);
+  py::class_<PowerSpectrumVADMetric, VADMetric, cref<PowerSpectrumVADMetric>>(m, "PowerSpectrumVADMetricPtr")
+      .def(py::init([](unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, const std::string& nm) {
+             return new PowerSpectrumVADMetric(fftLen, sampleRate, lowCutoff, highCutoff, nm);
+           }), py::arg("fftLen"), py::arg("sampleRate") = 16000.0, py::arg("lowCutoff") = -1.0, py::arg("highCutoff") = -1.0,
+           py::arg("nm") = "Power Spectrum VAD Metric")
+      .def("set_channel", [](PowerSpectrumVADMetric& v, py::object chan) { v.set_channel(as_fstream(chan)); }, py::arg("chan"))
+      .def("setChannel", [](PowerSpectrumVADMetric& v, py::object chan) { v.set_channel(as_fstream(chan)); }, py::arg("chan"))
+      .def("clear_channel", &PowerSpectrumVADMetric::clear_channel)
+      .def("clearChannel", &PowerSpectrumVADMetric::clear_channel)
+      .def("set_E0", &PowerSpectrumVADMetric::set_E0, py::arg("E0"))
+      .def("setE0", &PowerSpectrumVADMetric::set_E0, py::arg("E0"))
+      .def("get_metrics", [](PowerSpectrumVADMetric& v) -> py::object {
+             const gsl_vector* p = v.get_metrics();
+             if (!p) return py::none();
+             return py::array_t<double>((py::ssize_t)p->size, p->data);
+           })
+      .def("getMetrics", [](PowerSpectrumVADMetric& v) -> py::object {
+             const gsl_vector* p = v.get_metrics();
+             if (!p) return py::none();
+             return py::array_t<double>((py::ssize_t)p->size, p->data);
+           })
+      .def("lowX", &PowerSpectrumVADMetric::lowX)
+      .def("highX", &PowerSpectrumVADMetric::highX)
+      .def("binN", &PowerSpectrumVADMetric::binN);
+  py::class_<NormalizedEnergyMetric, PowerSpectrumVADMetric, cref<NormalizedEnergyMetric>>(m, "NormalizedEnergyMetricPtr")
+      .def(py::init([](unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, const std::string& nm) {
+             return new NormalizedEnergyMetric(fftLen, sampleRate, lowCutoff, highCutoff, nm);
+           }), py::arg("fftLen"), py::arg("sampleRate") = 16000.0, py::arg("lowCutoff") = -1.0, py::arg("highCutoff") = -1.0,
+           py::arg("nm") = "NormalizedEnergyMetric");
+  py::class_<TSPSVADMetric, PowerSpectrumVADMetric, cref<TSPSVADMetric>>(m, "TSPSVADMetricPtr")
+      .def(py::init([](unsigned fftLen, double sampleRate, double lowCutoff, double highCutoff, const std::string& nm) {
+             return new TSPSVADMetric(fftLen, sampleRate, lowCutoff, highCutoff, nm);
+           }), py::arg("fftLen"), py::arg("sampleRate") = 16000.0, py::arg("lowCutoff") = -1.0, py::arg("highCutoff") = -1.0,
+           py::arg("nm") = "TSPS VAD Metric");
+  py::class_<VAD, cref<VAD>>(m, "VADPtr")
+      .def("next", [](VAD& v, int frame_no) { return v.next(frame_no); }, py::arg("frame_no") = -5)
+      .def("__next__", [](VAD& v) { return v.next(-5); })
+      .def("__iter__", [](py::object self) { self.attr("reset")(); return self; })
+      .def("reset", [](VAD& v) { v.reset(); })
+      .def("frame", [](py::object self) { return view(self.cast<VAD&>().frame(), self); })
+      .def("next_speaker", [](VAD& v) { v.next_speaker(); })
+      .def("nextSpeaker", [](VAD& v) { v.next_speaker(); })
+      .def("frame_no", [](VAD& v) { return v.frame_no(); });
+  py::class_<SimpleEnergyVAD, VAD, cref<SimpleEnergyVAD>>(m, "SimpleEnergyVADPtr")
+      .def(py::init([](py::object samp, double threshold, double gamma) {
+             VectorComplexFeatureStreamPtr sp = as_cstream(samp);
+             return new SimpleEnergyVAD(sp, threshold, gamma);
+           }), py::arg("samp"), py::arg("threshold"), py::arg("gamma") = 0.98)
+      .def("spectral_energy", &SimpleEnergyVAD::spectral_energy)
+      .def("set_block_frames", [](SimpleEnergyVAD& v, long n) { v.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](SimpleEnergyVAD& v) { return v.block_frames(); })
+      .def("launches", [](SimpleEnergyVAD& v) { return v.launches(); });
+  py::class_<HangoverVADFeature, VectorFloatFeatureStream, cref<HangoverVADFeature>>(m, "HangoverVADFeaturePtr")
+      .def(py::init([as_metric](py::object source, py::object metric, double threshold, unsigned headN, unsigned tailN, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(source);
+             return new HangoverVADFeature(sp, as_metric(metric), threshold, headN, tailN, nm);
+           }), py::arg("source"), py::arg("metric"), py::arg("threshold") = 0.5, py::arg("headN") = 4, py::arg("tailN") = 10,
+           py::arg("nm") = "Hangover VAD Feature")
+      .def("reset", [](HangoverVADFeature& f) { f.reset(); })
+      .def("next_speaker", [](HangoverVADFeature& f) { f.next_speaker(); })
+      .def("nextSpeaker", [](HangoverVADFeature& f) { f.next_speaker(); })
+      .def("prefixN", &HangoverVADFeature::prefixN)
+      .def("set_block_frames", [](HangoverVADFeature& f, long n) { f.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](HangoverVADFeature& f) { return f.block_frames(); })
+      .def("launches", [](HangoverVADFeature& f) { return f.launches(); });
+  py::class_<HangoverMIVADFeature, HangoverVADFeature, cref<HangoverMIVADFeature>>(m, "HangoverMIVADFeaturePtr")
+      .def(py::init([as_metric](py::object source, py::object energyMetric, py::object mutualInformationMetric, py::object powerMetric,
+                                double energyThreshold, double mutualInformationThreshold, double powerThreshold, unsigned headN,
+                                unsigned tailN, const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(source);
+             return new HangoverMIVADFeature(sp, as_metric(energyMetric), as_metric(mutualInformationMetric), as_metric(powerMetric),
+                                             energyThreshold, mutualInformationThreshold, powerThreshold, headN, tailN, nm);
+           }), py::arg("source"), py::arg("energyMetric"), py::arg("mutualInformationMetric"), py::arg("powerMetric"),
+           py::arg("energyThreshold") = 0.5, py::arg("mutualInformationThreshold") = 0.5, py::arg("powerThreshold") = 0.5,
+           py::arg("headN") = 4, py::arg("tailN") = 10, py::arg("nm") = "Hangover MIVAD Feature")
+      .def("decision_metric", &HangoverMIVADFeature::decision_metric)
+      .def("decisionMetric", &HangoverMIVADFeature::decision_metric);
+  py::class_<HangoverMultiStageVADFeature, HangoverVADFeature, cref<HangoverMultiStageVADFeature>>(m, "HangoverMultiStageVADFeaturePtr")
+      .def(py::init([as_metric](py::object source, py::object energyMetric, double energyThreshold, unsigned headN, unsigned tailN,
+                                const std::string& nm) {
+             VectorFloatFeatureStreamPtr sp = as_fstream(source);
+             return new HangoverMultiStageVADFeature(sp, as_metric(energyMetric), energyThreshold, headN, tailN, nm);
+           }), py::arg("source"), py::arg("energyMetric"), py::arg("energyThreshold") = 0.5, py::arg("headN") = 4, py::arg("tailN") = 10,
+           py::arg("nm") = "HangoverMultiStageVADFeature")
+      .def("decision_metric", &HangoverMultiStageVADFeature::decision_metric)
+      .def("decisionMetric", &HangoverMultiStageVADFeature::decision_metric)
+      .def("set_metric", [as_metric](HangoverMultiStageVADFeature& f, py::object metricPtr, double threshold) { f.set_metric(as_metric(metricPtr), threshold); },
+           py::arg("metricPtr"), py::arg("threshold"))
+      .def("setMetric", [as_metric](HangoverMultiStageVADFeature& f, py::object metricPtr, double threshold) { f.set_metric(as_metric(metricPtr), threshold); },
+           py::arg("metricPtr"), py::arg("threshold"));
 }

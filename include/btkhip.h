@@ -922,6 +922,78 @@ int  btk_binaural_candidates(double min, double max, double width, float* out, i
 int  btk_binaural_threshold(int kind, int M, int nCand, int nWalk, const float* cands, const double* state, long long count,
                             double beta, double* threshold, double* cost, double* thresholds);
 
+/* ---- Voice activity detection: the energy family of sad/sad.cc ----------------------------------------------------------
+ * Every sum is float64 over float32 inputs in the reference's order, every comparison strict as there: energies, band powers,
+ * power / normalised-energy scores, every value and every frame number are the reference's bits (the TSPS score up to the
+ * device's float64 log).  A block cut anywhere continues from the state and gives the bits of one launch.
+ *
+ * btk_vad_frame_energy: energy[s][t] = sum_{n < D} |x[s][t][n]|^2 in index order (EnergyVADMetric::above_threshold_, :520-524;
+ *   is_complex: complex64 elements, re^2 + im^2 each, SimpleEnergyVAD::next :165-167).  Element n of frame t of stream s lies at
+ *   x + s stream_stride + t frame_stride + n elem_stride (in elements), so the producers' blocks are read as they lie: snapshot
+ *   rows complex64 [S][K][T_stride] (frame_stride 1, elem_stride T_stride), feature rows float32 [S][T][D] (D, 1), PCM (shift, 1).
+ *   energy [dev] float64 [S][e_stride].  Frame-minor rows may not overlap: T frame_stride <= elem_stride.
+ * btk_vad_band_limits [host]: lowX, highX, binN of MultiChannelVADMetric (:629-663): a negative cutoff means 0 / fftLen/2; the
+ *   low edge truncates, the high edge adds 0.5; a cutoff >= samplerate / 2 is BTK_ERR_DIMENSION.
+ * btk_vad_band_power: spec float32 power spectra, bin k of frame t of channel c of stream s at s stream_stride + c chan_stride +
+ *   t frame_stride + k bin_stride.  P[s][c][t] = (sum_{k = lowX .. highX} w_k spec[k]) / M, w_k = 1 for k == 0 or k == M/2 + 1,
+ *   else 2 (the reference tests fftLen2_ + 1, so the Nyquist bin is doubled; kept).  P [dev] float64 [S][C][o_stride] or NULL;
+ *   score, value [dev] float64 [S][o_stride] (score may be NULL); value = +1 / -1:
+ *     BTK_VAD_POWER       score = P_0 / sum_c P_c,                       value = score > E0 / C   (:731-736)
+ *     BTK_VAD_NORMALIZED  score = sqrt(P_0) / sum_c sqrt(P_c),           value = score > E0 / C   (:815-827)
+ *     BTK_VAD_TSPS        score = log(P_0 / (sum P - P_0)) - log(E0 / sum P), value = score > 0   (:1044-1054)
+ * btk_vad_energy_metric: EnergyVADMetric::next (:518-588) over energy [dev] float64 [S][e_stride]: value [dev] float64
+ *   [S][v_stride] = 1.0 where energy > sorted window[medianX], evaluated as #{window < energy} > medianX (a NaN energy, on which
+ *   the reference's qsort is undefined, is thereby never above and never below), else 0.0; the window takes the energy only while
+ *   recognizing == false && abovethresholdN == 0; then the head/tail counters move.  state [dev], per stream
+ *   btk_vad_energy_metric_state_bytes(energiesN) = 8 (4 + energiesN) bytes: int64 {ring position, recognizing, abovethresholdN,
+ *   belowThresholdN}, then the float64 window as a ring whose oldest entry is at the ring position.  The caller initialises it:
+ *   zeros and initialEnergy; a ring position outside 0 .. energiesN - 1 is the caller's error and is not checked on the device.  medianX = unsigned(threshold energiesN) must be < energiesN.
+ * btk_vad_simple_energy: SimpleEnergyVAD::next (:165-171) over energy rows: s <- gamma s + (1 - gamma) E (two rounded products,
+ *   one rounded sum), is_speech [dev] int32 [S][o_stride] = E / s > threshold, smoothed [dev] float64 [S][o_stride] or NULL = s;
+ *   state [dev] float64 [S] = s (spectral_energy_, 0 at the start and after next_speaker()).
+ * btk_vad_hangover: the detection rule and the head/tail machine of HangoverVADFeature::next (:1763-1843) on R <= 8 rows of metric
+ *   values, values [host] R pointers to [dev] float64 [S][v_stride], thresholds [host] float64 [R]:
+ *     BTK_VAD_RULE_SINGLE      values[0] > thresholds[0]                                   (:1763-1771)
+ *     BTK_VAD_RULE_MI          R == 3, HangoverMIVADFeature::above_threshold_ (:1859-1885), codes -1, 2, 3, -3
+ *     BTK_VAD_RULE_MULTISTAGE  :1910-1951: never with R < 3; values[0] < 0.5 vetoes (code -1); else the first m >= 1 with
+ *                              values[m] > 0.5 wins (code m + 1); else code -R
+ *   decision [dev] int32 [S][d_stride] or NULL: decision_metric() after each frame (a rule that assigns none leaves the state's).
+ *   state [dev] int64 [S][8]: {abovethresholdN, belowThresholdN, recognizing, frames seen, start, end, ended, decision_metric};
+ *   the caller starts it as {0, 0, 0, 0, -1, -1, 0, 0}.  start = q - headN + 1 for the first frame q that ends headN consecutive
+ *   detections (prefixN()); end = the frame on which the tailN-th consecutive miss falls (exclusive); frame numbers count from
+ *   the state's frames seen.  After `ended` the machine rests (decisions are still written).  restart != 0: an end clears the
+ *   counters and the machine goes on; every (start, end) completed in this call goes to segments [dev] int64 [S][max_seg][2] in
+ *   order and their number to nseg [dev] int32 [S] (it may exceed max_seg: those beyond are not written); a segment still open
+ *   stays in the state's start.  headN == 0 is BTK_ERR_DIMENSION.
+ * btk_vad_gather: rows [start, end) of the state's segment (end < 0: still open) that lie in src [dev] float32 [S][T][D], whose
+ *   row 0 is frame frame_base, to dst [dev] float32 [S][dst_rows][D] at row (frame - start); count [dev] int64 [S] or NULL: rows
+ *   copied by this call.  Rows beyond dst_rows are not copied.
+ * Limits: 1 <= S <= 65535, 0 <= T <= the row strides, 1 <= energiesN <= 1024, 1 <= C <= 64, 2 <= M <= 2048,
+ * 0 <= lowX <= highX <= M/2, 1 <= D <= 65536: BTK_ERR_DIMENSION beyond them, BTK_ERR_PARAMETER for a null pointer or an unknown
+ * kind or rule; nothing is launched and the state stays untouched.                                                            */
+#define BTK_VAD_POWER 0
+#define BTK_VAD_NORMALIZED 1
+#define BTK_VAD_TSPS 2
+#define BTK_VAD_RULE_SINGLE 0
+#define BTK_VAD_RULE_MI 1
+#define BTK_VAD_RULE_MULTISTAGE 2
+int  btk_vad_frame_energy(const void* x, int is_complex, int S, int D, long T, long stream_stride, long frame_stride,
+                          long elem_stride, double* energy, long e_stride, void* stream);
+int  btk_vad_band_limits(int fftLen, double samplerate, double lowCutoff, double highCutoff, int* lowX, int* highX, int* binN);
+int  btk_vad_band_power(const float* spec, int kind, int S, int C, int M, long T, long stream_stride, long chan_stride,
+                        long frame_stride, long bin_stride, int lowX, int highX, double E0, double* P, double* score,
+                        double* value, long o_stride, void* stream);
+long btk_vad_energy_metric_state_bytes(int energiesN);
+int  btk_vad_energy_metric(const double* energy, long e_stride, int S, long T, int energiesN, int medianX, unsigned headN,
+                           unsigned tailN, void* state, double* value, long v_stride, void* stream);
+int  btk_vad_simple_energy(const double* energy, long e_stride, int S, long T, double gamma, double threshold, double* state,
+                           int* is_speech, double* smoothed, long o_stride, void* stream);
+int  btk_vad_hangover(const double* const* values, const double* thresholds, int R, int rule, int S, long T, long v_stride,
+                      unsigned headN, unsigned tailN, int restart, long long* state, int* decision, long d_stride,
+                      long long* segments, int max_seg, int* nseg, void* stream);
+int  btk_vad_gather(const float* src, int S, long T, int D, long frame_base, const long long* hangover_state, float* dst,
+                    long dst_rows, long long* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import sys
 
 REF = "/root/reference/btk20_src"
 FILES = ["feature/feature.i", "modulated/modulated.i", "beamformer/beamformer.i", "postfilter/postfilter.i",
-         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i", "convolution/convolution.i"]
+         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i", "convolution/convolution.i", "sad/sad.i"]
 CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
            "LogFeature", "CepstralFeature", "StorageFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
            "SubbandBeamformer", "SubbandDS", "SubbandGSC", "SubbandGSCRLS", "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter",
@@ -23,8 +23,14 @@ CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature"
            "DTDBlockKalmanFilterEchoCancellationFeature", "OverlapAdd", "OverlapSave", "SpectralSubtractor", "WienerFilter",
            "HighPassFilter", "NormalFFTAnalysisBank", "PerfectReconstructionFFTAnalysisBank", "PerfectReconstructionFFTSynthesisBank",
            "DelayFeature", "BinaryMaskFilter", "KimBinaryMaskFilter", "KimITDThresholdEstimator", "IIDBinaryMaskFilter",
-           "IIDThresholdEstimator", "FDIIDThresholdEstimator"]
-SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current"}
+           "IIDThresholdEstimator", "FDIIDThresholdEstimator", "SpectralPowerFloatFeature", "VADMetric", "EnergyVADMetric",
+           "FloatMultiChannelVADMetric", "PowerSpectrumVADMetric", "NormalizedEnergyMetric", "TSPSVADMetric", "VAD", "SimpleEnergyVAD",
+           "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature"]
+SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current",
+        # the log-file functions of VADMetric (_LOG_SAD_) are not carried over
+        "openLogFile", "writeLog", "closeLogFile", "initScore", "setScore", "getAverageScore", "initScores", "getScores"}
+# an interface class the engine does not bind: its methods are those of the bound class that derives from it
+MERGED = {"FloatMultiChannelVADMetric": "PowerSpectrumVADMetric"}
 
 
 def strip_comments(t):
@@ -131,7 +137,7 @@ def main():
                 mm = re.match(r"(?:virtual\s+|static\s+)?(?:[\w:<>]+[\s\*&]+)+?(\w+)\s*\((.*)\)\s*(?:const)?$", st)
                 if not mm or mm.group(1) in SKIP or mm.group(1) == base or mm.group(1).startswith("~"):
                     continue
-                methods.setdefault(cname + "Ptr", {}).setdefault(mm.group(1), params(mm.group(2)))
+                methods.setdefault(MERGED.get(cname, cname) + "Ptr", {}).setdefault(mm.group(1), params(mm.group(2)))
     out = ['"""Parameter names of the reference\'s SWIG interface, GENERATED by tools/gen_swig_signatures.py from btk20_src/*/*.i',
            '(%feature("kwargs"): scripts may call every method with these names).  (name, default) per parameter; default "required" = no',
            'default, Ellipsis = optional with a default the .i file writes as an expression (left to the binding).  Do not edit."""', "",
