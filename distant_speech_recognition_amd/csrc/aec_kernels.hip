@@ -25,6 +25,7 @@
 //               two workgroup barriers per frame.  K lives in LDS for the block when (M/2+1) P^2 16 B fits, otherwise it is
 //               updated in place in the exported state (L2-resident).  Workgroups never wait for each other.
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include <cstdint>
 
 namespace {
@@ -35,58 +36,6 @@ constexpr long AEC_FRAME_FROM_STATE = -(1L << 30);
 constexpr int DTD_NT = 1024;            // kind 3: threads per stream
 constexpr int DTD_NW = DTD_NT / 64;
 constexpr size_t AEC_LDS_BUDGET = 160 * 1024 - 512;
-
-struct zd { double x, y; };
-__device__ __forceinline__ zd zmk(double x, double y) { zd r; r.x = x; r.y = y; return r; }
-__device__ __forceinline__ zd zadd(zd a, zd b) { return zmk(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ zd zsub(zd a, zd b) { return zmk(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ zd zconj(zd a) { return zmk(a.x, -a.y); }
-__device__ __forceinline__ zd zscale(zd a, double s) { return zmk(a.x * s, a.y * s); }
-__device__ __forceinline__ zd zmul(zd a, zd b) { return zmk(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)); }
-__device__ __forceinline__ double zabs2(zd a) { return fma(a.x, a.x, a.y * a.y); }
-// c + a b
-__device__ __forceinline__ zd zfma(zd a, zd b, zd c)
-{
-  c.x = fma(a.x, b.x, c.x); c.x = fma(-a.y, b.y, c.x);
-  c.y = fma(a.x, b.y, c.y); c.y = fma(a.y, b.x, c.y);
-  return c;
-}
-// c + a conj(b)
-__device__ __forceinline__ zd zfmabc(zd a, zd b, zd c)
-{
-  c.x = fma(a.x, b.x, c.x); c.x = fma(a.y, b.y, c.x);
-  c.y = fma(a.y, b.x, c.y); c.y = fma(-a.x, b.y, c.y);
-  return c;
-}
-
-template <int CTRL> __device__ __forceinline__ double dpp_d(double v)
-{
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v)
-{
-  v += dpp_d<0xB1>(v);                  // quad_perm [1,0,3,2]
-  v += dpp_d<0x4E>(v);                  // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ zd quad_sum(zd v) { return zmk(quad_sum(v.x), quad_sum(v.y)); }
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ zd wave_sum(zd v) { return zmk(wave_sum(v.x), wave_sum(v.y)); }
-// value of a wavefront-uniform lane
-__device__ __forceinline__ double lane_d(double v, int lane)
-{
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ zd lane_z(zd v, int lane) { return zmk(lane_d(v.x, lane), lane_d(v.y, lane)); }
 
 struct AecParams {
   int kind;

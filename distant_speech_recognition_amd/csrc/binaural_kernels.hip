@@ -19,6 +19,7 @@
 // Decisions (phases, magnitudes, comparisons) and every sum the reference keeps in double are float64; only the mask recursion
 // and the masked output are float32, as prevMu_ and this project's subband samples are.
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include <cmath>
 #include <cstdint>
 
@@ -29,12 +30,7 @@ constexpr int BN_MAXCAND = 4096;
 constexpr int BN_MAXCHUNKS = 512;
 constexpr int BN_MINFR = 4;
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_or(float identity, float v)
-{
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, identity), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
-// one step of the inclusive scan of affine maps v -> a v + b; lanes without a source keep the identity (1, 0); a = 0 forgets
+// one step of the inclusive scan (affine_scan_schedule, wave_ops.h) of affine maps v -> a v + b; lanes without a source keep the identity (1, 0); a = 0 forgets
 // its past (see ss_kernels.hip)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void affine_scan_step(float& a, float& b)
@@ -45,12 +41,7 @@ __device__ __forceinline__ void affine_scan_step(float& a, float& b)
 }
 __device__ __forceinline__ void affine_scan(float& a, float& b)
 {
-  affine_scan_step<0x111, 0xF>(a, b);      // row_shr:1
-  affine_scan_step<0x112, 0xF>(a, b);      // row_shr:2
-  affine_scan_step<0x114, 0xF>(a, b);      // row_shr:4
-  affine_scan_step<0x118, 0xF>(a, b);      // row_shr:8
-  affine_scan_step<0x142, 0xA>(a, b);      // row_bcast:15 -> rows 1, 3
-  affine_scan_step<0x143, 0xC>(a, b);      // row_bcast:31 -> rows 2, 3
+  affine_scan_schedule([&](auto ctrl, auto rows) { affine_scan_step<decltype(ctrl)::value, decltype(rows)::value>(a, b); });
 }
 
 __device__ __forceinline__ long bn_clamp(long t, long T) { return t < 0 ? 0 : (t >= T ? T - 1 : t); }

@@ -10,17 +10,12 @@
 // then partly substituted: callers that need it reload it).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "wave_ops.h"
 
 namespace cholb {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int CH_NB = 16;              // panel width
 constexpr int CH_LD = CH_NB + 1;       // padded row (float2): conflict-free row-per-lane access
-
-__device__ __forceinline__ float2 cmul_conj_b(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
-// value of lane `l` (compile-time) broadcast to the wavefront through an SGPR
-__device__ __forceinline__ float lane_value(float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); }
-
 
 inline size_t lds_bytes(int P) { return sizeof(float2) * (size_t)((P + 1) & ~1) + sizeof(float) * 512 + sizeof(float2) * (size_t)P * CH_LD; }
 

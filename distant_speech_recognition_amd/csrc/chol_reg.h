@@ -19,10 +19,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fft_packed.h"
+#include "wave_ops.h"
 
 namespace cholr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int NTH = 512, NWAVE = 8;
 constexpr int NT_MAX = 17;                                          // tile rows of 16: P + 1 <= 272
 constexpr int NTILE_MAX = NT_MAX * (NT_MAX + 1) / 2;                // 153
@@ -41,9 +41,6 @@ constexpr int OFF_YV = OFF_DSAVE + NT_MAX * 16 * LD;                // [ROWS]
 constexpr int OFF_XV = OFF_YV + ROWS;                               // [ROWS]
 constexpr int OFF_DIAG = OFF_XV + ROWS;                             // float [ROWS] (+ 16 floats of reduction scratch, + the pivot-failure flag)
 inline size_t lds_bytes() { return sizeof(float2) * (size_t)OFF_DIAG + sizeof(float) * (ROWS + 32); }
-
-__device__ __forceinline__ float2 cmul_conj_b(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
-__device__ __forceinline__ float lane_value(float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); }
 
 // mat [P][P] row-major (lower triangle read, never written); rhs_conj(p) = conj(r[p]); diag(p) = the (real) diagonal entry to use.
 // On success the solution of A x = r is in xv[0..P) (LDS, returned pointer) after a workgroup barrier.  Returns nullptr when a pivot

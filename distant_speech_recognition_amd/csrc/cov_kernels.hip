@@ -20,13 +20,13 @@
 // it (pybeamformer.py:1080, :1137-1147).
 #include <algorithm>
 #include "btk_internal.h"
+#include "wave_ops.h"
 
 namespace {
 
 constexpr int CT = 32;                 // frames per LDS tile
 constexpr int CLD = CT + 1;            // padded row (float2 units)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float tile_weight(const float* __restrict__ wt, const float* __restrict__ wf, long t, long T)
 {

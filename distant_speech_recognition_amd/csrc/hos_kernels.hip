@@ -21,6 +21,7 @@
 // so two runs give the same bits.  hos_minimize_kernel runs the whole Polak-Ribiere+ / Armijo iteration of a bin inside its
 // workgroup: the vectors of the optimiser live in LDS, every decision is taken by lane 0 and broadcast through LDS.
 #include "btk_internal.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -66,13 +67,6 @@ struct hos_lds {
   double sc[4];
   int flag;
 };
-
-__device__ __forceinline__ double hos_wave_sum(double v)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // number of selected frames of the block (the reference's len(self._observations))
 template <int NS>
@@ -249,8 +243,8 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
       for (int i = 0; i < HOS_CPW; i++) {
         const int n = wave + HOS_WAVES * i;
         if (n < N) {
-          const double r0 = hos_wave_sum(a2r[i]), r1 = hos_wave_sum(a2i[i]);
-          const double r2 = hos_wave_sum(a4r[i]), r3 = hos_wave_sum(a4i[i]);
+          const double r0 = wave_sum(a2r[i]), r1 = wave_sum(a2i[i]);
+          const double r2 = wave_sum(a4r[i]), r3 = wave_sum(a4i[i]);
           if (lane == 0) { L.v2[sp][n] = make_double2(r0, r1); L.v4[sp][n] = make_double2(r2, r3); }
         }
       }
@@ -260,11 +254,11 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
   // ---- lane partials -> wavefront partials -> totals, in a fixed order
 #pragma unroll
   for (int s = 0; s < NS; s++) {
-    const double r2 = hos_wave_sum(s2[s]), r4 = hos_wave_sum(s4[s]);
+    const double r2 = wave_sum(s2[s]), r4 = wave_sum(s4[s]);
     if (lane == 0) { L.part[wave][2 * s] = r2; L.part[wave][2 * s + 1] = r4; }
   }
   {
-    const double r2 = hos_wave_sum(m2), r4 = hos_wave_sum(m4);
+    const double r2 = wave_sum(m2), r4 = wave_sum(m4);
     if (lane == 0) { L.part[wave][2 * NS] = r2; L.part[wave][2 * NS + 1] = r4; }
   }
   __syncthreads();
@@ -303,7 +297,7 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
         p2r = b.x * u.x - b.y * u.y; p2i = b.x * u.y + b.y * u.x;
         p4r = b.x * v.x - b.y * v.y; p4i = b.x * v.y + b.y * v.x;
       }
-      p2r = hos_wave_sum(p2r); p2i = hos_wave_sum(p2i); p4r = hos_wave_sum(p4r); p4i = hos_wave_sum(p4i);
+      p2r = wave_sum(p2r); p2i = wave_sum(p2i); p4r = wave_sum(p4r); p4i = wave_sum(p4i);
       if (lane == 0) {
         const long long pn = a.pN ? a.pN[(long)k * NS + s] : 0;
         const double ntot = (double)(pn + L.tsel);

@@ -18,6 +18,7 @@
 //   2. zelinski_iir_kernel   : one wavefront per (stream, bin) row; 64-frame chunks scanned with a
 //                              Hillis-Steele linear-recurrence scan; gain applied to Y in place.
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include <cstdlib>
 
 namespace {
@@ -67,15 +68,8 @@ void bf_apply_stats_kernel(const float2* __restrict__ W, long w_stream_stride,
   Ee[o] = e;
 }
 
-// Inclusive wave-wide scan of the affine maps v -> a v + b[i] (one multiplier, NB offsets) in the DPP network: four row_shr steps
-// inside the 16-lane rows, then the row totals travel with row_bcast:15 (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).
-// Lanes without a source keep the identity map (`old` operand), so no lane tests are needed.  The shuffle form of the same
-// scan was 30 dependent ds_bpermute round trips per 64-frame chunk.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_or(float identity, float v)
-{
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, identity), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
+// Inclusive wave-wide scan of the affine maps v -> a v + b[i] (one multiplier, NB offsets) in the DPP network
+// (affine_scan_schedule, wave_ops.h).
 template <int NB, int CTRL, int ROW_MASK>
 __device__ __forceinline__ void affine_scan_step(float& a, float (&b)[NB])
 {
@@ -90,12 +84,7 @@ __device__ __forceinline__ void affine_scan_step(float& a, float (&b)[NB])
 template <int NB>
 __device__ __forceinline__ void affine_scan(float& a, float (&b)[NB])
 {
-  affine_scan_step<NB, 0x111, 0xF>(a, b);      // row_shr:1
-  affine_scan_step<NB, 0x112, 0xF>(a, b);      // row_shr:2
-  affine_scan_step<NB, 0x114, 0xF>(a, b);      // row_shr:4
-  affine_scan_step<NB, 0x118, 0xF>(a, b);      // row_shr:8
-  affine_scan_step<NB, 0x142, 0xA>(a, b);      // row_bcast:15 -> rows 1, 3
-  affine_scan_step<NB, 0x143, 0xC>(a, b);      // row_bcast:31 -> rows 2, 3
+  affine_scan_schedule([&](auto ctrl, auto rows) { affine_scan_step<NB, decltype(ctrl)::value, decltype(rows)::value>(a, b); });
 }
 
 // One wavefront per (s,k).  frame_base = number of frames this post-filter has already produced

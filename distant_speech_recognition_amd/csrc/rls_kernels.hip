@@ -21,50 +21,13 @@
 // plus a DPP quad reduction, and the rank-1 update is elementwise on both copies.  Vectors that every thread
 // needs (P x, x^H P, w) go through LDS; x_t is staged in 16-frame tiles (128-byte rows) with register prefetch.
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include <cstdlib>
 
 namespace {
 
 constexpr int RTB = 16;                 // frames per LDS tile
 constexpr int RLD = RTB + 1;            // padded row (float2 units)
-
-struct zd { double x, y; };
-__device__ __forceinline__ zd zmk(double x, double y) { zd r; r.x = x; r.y = y; return r; }
-__device__ __forceinline__ zd zadd(zd a, zd b) { return zmk(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ zd zsub(zd a, zd b) { return zmk(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ zd zconj(zd a) { return zmk(a.x, -a.y); }
-__device__ __forceinline__ zd zscale(zd a, double s) { return zmk(a.x * s, a.y * s); }
-__device__ __forceinline__ zd zmul(zd a, zd b) { return zmk(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)); }
-// c + a b
-__device__ __forceinline__ zd zfma(zd a, zd b, zd c)
-{
-  c.x = fma(a.x, b.x, c.x); c.x = fma(-a.y, b.y, c.x);
-  c.y = fma(a.x, b.y, c.y); c.y = fma(a.y, b.x, c.y);
-  return c;
-}
-// c + conj(a) b
-__device__ __forceinline__ zd zfmac(zd a, zd b, zd c)
-{
-  c.x = fma(a.x, b.x, c.x); c.x = fma(a.y, b.y, c.x);
-  c.y = fma(a.x, b.y, c.y); c.y = fma(-a.y, b.x, c.y);
-  return c;
-}
-__device__ __forceinline__ zd zinv(zd a) { const double d = 1.0 / fma(a.x, a.x, a.y * a.y); return zmk(a.x * d, -a.y * d); }
-
-template <int CTRL> __device__ __forceinline__ double dpp_d(double v)
-{
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v)
-{
-  v += dpp_d<0xB1>(v);                  // quad_perm [1,0,3,2]
-  v += dpp_d<0x4E>(v);                  // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ zd quad_sum(zd v) { return zmk(quad_sum(v.x), quad_sum(v.y)); }
 
 struct RlsParams {
   int mode;

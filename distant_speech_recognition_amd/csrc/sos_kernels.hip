@@ -16,23 +16,11 @@
 // the resulting rank-one matrix with the largest diagonal, w = L^-H v / |v|  (w^H Rn w = 1 like scipy's eigh).
 // A target covariance without a positive trace is replaced by I / N: finite weights, not counted as failed.
 #include "btk_internal.h"
+#include "zd.h"
 
 namespace {
 
-struct zd { double x, y; };
 typedef double d4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ zd zmk(double x, double y) { zd r; r.x = x; r.y = y; return r; }
-__device__ __forceinline__ zd zconj(zd a) { return zmk(a.x, -a.y); }
-__device__ __forceinline__ zd zscale(zd a, double s) { return zmk(a.x * s, a.y * s); }
-// c + a b
-__device__ __forceinline__ zd zfma(zd a, zd b, zd c)
-{
-  c.x = fma(a.x, b.x, c.x); c.x = fma(-a.y, b.y, c.x);
-  c.y = fma(a.x, b.y, c.y); c.y = fma(a.y, b.x, c.y);
-  return c;
-}
-// c - a b
-__device__ __forceinline__ zd zfms(zd a, zd b, zd c) { return zfma(zmk(-a.x, -a.y), b, c); }
 
 constexpr int SOS_NT = 256;
 constexpr int SOS_TAIL = 2 * SOS_NT * 8 + 64;      // reduction scratch ahead of the matrices in dynamic LDS

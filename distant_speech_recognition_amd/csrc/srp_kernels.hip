@@ -18,10 +18,10 @@
 //                      lane per frame, and the energy gate of :3148-3155.
 //   srp_acc_kernel   : accRPs_ (:3162) in float64, one wavefront per (stream, direction), coalesced loads, frames added in index order.
 #include "btk_internal.h"
+#include "wave_ops.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SRP_FT = 32;             // frames per wavefront strip (the j extent of the 32x32x2 instruction)
 constexpr int SRP_WAVES = 4;           // wavefronts (strips) per workgroup; they share nothing

@@ -25,6 +25,7 @@
 // steps or the per-lane carries, and its channel loop unrolls over independent loads.
 // The outputs are written once and not read again by these kernels: non-temporal stores; X is read once: non-temporal loads.
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include <cstdint>
 
 namespace {
@@ -36,12 +37,7 @@ constexpr int SS_UNROLL = 4;
 // per channel: a = alpha (< 0: averaging channel), b = float(1 - alpha) rounded from float64
 struct ss_alpha_t { float a[SS_MAXC]; float b[SS_MAXC]; };
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_or(float identity, float v)
-{
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, identity), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
-}
-// One step of the inclusive scan of NB independent sequences of affine maps v -> a[i] v + b[i]: lanes without a source keep the
+// One step of the inclusive scan (affine_scan_schedule, wave_ops.h) of NB independent sequences of affine maps v -> a[i] v + b[i]: lanes without a source keep the
 // identity map (1, 0).  A map with a = 0 forgets its past whatever that is (a NaN estimate is REPLACED by a first sample, as the
 // reference's memcpy does), hence the select instead of 0 x p.
 // Stated deviation: the select acts on every map whose multiplier is 0, composed maps included.  The reference computes
@@ -63,12 +59,7 @@ __device__ __forceinline__ void affine_scan_step(float (&a)[NB], float (&b)[NB])
 template <int NB>
 __device__ __forceinline__ void affine_scan(float (&a)[NB], float (&b)[NB])
 {
-  affine_scan_step<NB, 0x111, 0xF>(a, b);      // row_shr:1
-  affine_scan_step<NB, 0x112, 0xF>(a, b);      // row_shr:2
-  affine_scan_step<NB, 0x114, 0xF>(a, b);      // row_shr:4
-  affine_scan_step<NB, 0x118, 0xF>(a, b);      // row_shr:8
-  affine_scan_step<NB, 0x142, 0xA>(a, b);      // row_bcast:15 -> rows 1, 3
-  affine_scan_step<NB, 0x143, 0xC>(a, b);      // row_bcast:31 -> rows 2, 3
+  affine_scan_schedule([&](auto ctrl, auto rows) { affine_scan_step<NB, decltype(ctrl)::value, decltype(rows)::value>(a, b); });
 }
 // the chunk's map applied to the float64 carry
 __device__ __forceinline__ double affine_apply(float a, float b, double carry)

@@ -15,6 +15,7 @@
 // lane's pair come from LDS.  The per-pair geometry lies in LDS too.
 #include <cmath>
 #include "btk_internal.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -22,14 +23,6 @@ constexpr int TRACK_LANES = 64;
 constexpr int TRACK_MAX_TILE = 32;                  // frames per LDS tile at most
 constexpr long TRACK_LDS_BYTES = 48 * 1024;         // per workgroup: P * (48 + 8 tile) bytes
 constexpr int TRACK_GAMMA_ITMAX = 20000;            // both expansions need O(sqrt(a)) terms; a = nobs / 2
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-  // butterfly: every lane ends with the same bits (each step adds the same two values in either order)
-#pragma unroll
-  for (int m = TRACK_LANES / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, TRACK_LANES);
-  return v;
-}
 
 // regularised lower incomplete gamma P(a, x): the series for x < a + 1, the continued fraction (modified Lentz) otherwise
 __device__ double track_gammainc(double a, double x)

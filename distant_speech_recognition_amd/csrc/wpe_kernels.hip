@@ -16,14 +16,13 @@
 //   wpe_rvec_kernel    : r_c
 //   wpe_solve_kernel   : diagonal bias + loading + in-place Cholesky (matrix in global memory / L2) + solves
 #include "btk_internal.h"
+#include "wave_ops.h"
 #include "chol_blocked.h"
 #include "chol_reg.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int WT_ = 32;                // frames per LDS tile
 
 struct WpeGeom { int K, C, L, lowerN, lower_bw, upper_bw; long T_stride, T; };

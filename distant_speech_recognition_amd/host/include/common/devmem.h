@@ -7,6 +7,9 @@
 //     stream has seen its largest block, a block costs no hipMalloc / hipHostMalloc / hipFree;
 //   * uploads come from pinned memory (the analysis banks keep their sample windows there), downloads go to pinned memory,
 //     both as hipMemcpyAsync on the node stream.
+// Everything declared here is defined in src/node_runtime.cc, together with the helpers the node files share (src/node_runtime.h:
+// error mapping, streams, copies, counters).  A new module includes that header; its device code includes csrc/wave_ops.h and
+// csrc/zd.h for the wavefront helpers and the float64 complex type.
 #pragma once
 #include <cstddef>
 

@@ -9,43 +9,23 @@
 #include <cstring>
 
 #include "aec/aec.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
-hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
+using btknode::check_abi;
+using btknode::check_hip;
+using btknode::nstream;
+using btknode::d2h;
+using btknode::even_pitch;
+
+// local: unlike btknode::dev_alloc, the canceller's state blocks have never counted into btk_node_alloc_counts()
 void* dev_alloc(size_t bytes)
 {
   void* p = NULL;
   check_hip(hipMalloc(&p, bytes ? bytes : 16), "hipMalloc");
   return p;
 }
-void d2h(void* h, const void* d, size_t n)
-{
-  if (!n) return;
-  check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
-  btk_node_count_d2h(n);
-  btk_node_synchronize();
-}
-long even_pitch(long frames) { return frames + (frames & 1); }
 
 }  // namespace
 

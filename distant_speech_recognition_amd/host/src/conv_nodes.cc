@@ -8,35 +8,13 @@
 #include "convolution/convolution.h"
 #include "feature/feature.h"
 #include "btkhip.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
-
-long conv_default_block_frames()
-{
-  const char* e = getenv("BTK_CONV_BLOCK_FRAMES");
-  const long v = (e && *e) ? atol(e) : 0;
-  return v > 0 ? v : 64;
-}
+using btknode::check_abi;
+using btknode::check_hip;
+using btknode::env_block_frames;
 
 bool pow2(unsigned v) { return v && !(v & (v - 1)); }
 
@@ -46,7 +24,7 @@ BlockConvolution::BlockConvolution(const VectorFloatFeatureStreamPtr& samp, cons
                                    bool save, const String& nm, long block_frames)
     : VectorFloatFeatureStream(out_size, nm), N_(0), Lk_(0), Bp_(0), Q_(0), L_(samp->size()), P_((unsigned)impulseResponse->size),
       samp_(samp), sample_(dynamic_cast<SampleFeature*>(samp_.operator->())), save_(save), have_spectra_(false),
-      block_frames_(block_frames > 0 ? block_frames : conv_default_block_frames()), blk_n_(0), blk_pos_(0), launches_(0)
+      block_frames_(block_frames > 0 ? block_frames : env_block_frames("BTK_CONV_BLOCK_FRAMES", 64)), blk_n_(0), blk_pos_(0), launches_(0)
 {
   // the taps arrive as float64 and are rounded to float32 for the device
   h_.resize(P_);
@@ -67,7 +45,7 @@ BlockConvolution::BlockConvolution(const VectorFloatFeatureStreamPtr& samp, cons
 
 void BlockConvolution::set_block_frames(long n)
 {
-  block_frames_ = n > 0 ? n : conv_default_block_frames();
+  block_frames_ = n > 0 ? n : env_block_frames("BTK_CONV_BLOCK_FRAMES", 64);
 }
 
 void BlockConvolution::reset()

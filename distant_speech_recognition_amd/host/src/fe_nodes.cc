@@ -9,36 +9,14 @@
 
 #include "feature/feature.h"
 #include "btkhip.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
-hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
-
-long fe_default_block_frames()
-{
-  const char* e = getenv("BTK_FE_BLOCK_FRAMES");
-  const long v = (e && *e) ? atol(e) : 0;
-  return v > 0 ? v : 64;
-}
+using btknode::check_abi;
+using btknode::check_hip;
+using btknode::nstream;
+using btknode::env_block_frames;
 
 void check_frame_no(int frame_no, int current, const String& name)
 {
@@ -218,7 +196,7 @@ void FFTFeature::fe_advance(long n, const float* last_half)
 
 // ================================================================================ FeStageNode: the block service
 FeStageNode::FeStageNode(int stage)
-    : tables_dirty_(true), stage_(stage), below_(NULL), fft_(NULL), block_frames_(fe_default_block_frames()), blk_n_(0), blk_pos_(0),
+    : tables_dirty_(true), stage_(stage), below_(NULL), fft_(NULL), block_frames_(env_block_frames("BTK_FE_BLOCK_FRAMES", 64)), blk_n_(0), blk_pos_(0),
       launches_(0)
 {
 }
@@ -229,7 +207,7 @@ void FeStageNode::fe_wire_(FeStageNode* below, FFTFeature* fft)
   fft_ = fft;
 }
 
-void FeStageNode::set_block_frames(long n) { block_frames_ = n > 0 ? n : fe_default_block_frames(); }
+void FeStageNode::set_block_frames(long n) { block_frames_ = n > 0 ? n : env_block_frames("BTK_FE_BLOCK_FRAMES", 64); }
 
 FFTFeature* FeStageNode::root_() const
 {

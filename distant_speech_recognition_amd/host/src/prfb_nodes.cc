@@ -12,28 +12,12 @@
 #include "modulated/modulated.h"
 #include "feature/feature.h"
 #include "btkhip.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
+using btknode::check_abi;
+using btknode::check_hip;
 
 bool pow2(unsigned v) { return v && !(v & (v - 1)); }
 

@@ -8,30 +8,15 @@
 
 #include "sad/sad.h"
 #include "btkhip.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
-hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
+using btknode::check_abi;
+using btknode::check_hip;
+using btknode::nstream;
 
+// local: unlike btknode::d2h_async / h2d_async these issue zero-byte copies too and name the VAD in their error text
 void download(void* h, const void* d, size_t bytes, hipStream_t st)
 {
   check_hip(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st), "VAD download");
@@ -44,12 +29,7 @@ void upload(void* d, const void* h, size_t bytes, hipStream_t st)
 
 }  // namespace
 
-long btk_vad_default_block_frames()
-{
-  const char* e = getenv("BTK_VAD_BLOCK_FRAMES");
-  const long v = (e && *e) ? atol(e) : 0;
-  return v > 0 ? v : 256;
-}
+long btk_vad_default_block_frames() { return btknode::env_block_frames("BTK_VAD_BLOCK_FRAMES", 256); }
 
 // ================================================================================ VADMetric: the block service
 VADMetric::VADMetric()

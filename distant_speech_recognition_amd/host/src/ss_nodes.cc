@@ -9,47 +9,17 @@
 
 #include "postfilter/spectralsubtraction.h"
 #include "postfilter/postfilter.h"
+#include "node_runtime.h"
 
 namespace {
 
-void check_abi(int rc)
-{
-  if (rc == BTK_OK) return;
-  const char* msg = btk_last_error();
-  switch (rc) {
-    case BTK_ERR_DIMENSION: throw jdimension_error("%s", msg);
-    case BTK_ERR_CONSISTENCY: throw jconsistency_error("%s", msg);
-    case BTK_ERR_ALLOCATION: throw jallocation_error("%s", msg);
-    case BTK_ERR_PARAMETER: throw jparameter_error("%s", msg);
-    case BTK_ERR_NUMERIC: throw jnumeric_error("%s", msg);
-    default: throw j_error("%s", msg);
-  }
-}
-void check_hip(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return;
-  if (e == hipErrorOutOfMemory) throw jallocation_error("%s: %s", what, hipGetErrorString(e));
-  throw j_error("%s: %s", what, hipGetErrorString(e));
-}
-hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
-void d2h(void* h, const void* d, size_t n)
-{
-  if (!n) return;
-  check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, nstream()), "hipMemcpyAsync D2H");
-  btk_node_count_d2h(n);
-  btk_node_synchronize();
-}
-void h2d(void* d, const void* h, size_t n)
-{
-  if (!n) return;
-  check_hip(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, nstream()), "hipMemcpyAsync H2D");
-  btk_node_synchronize();
-}
-void d2d(void* dst, const void* src, size_t n)
-{
-  if (n) check_hip(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, nstream()), "hipMemcpyAsync D2D");
-}
-long even_pitch(long frames) { return frames + (frames & 1); }
+using btknode::check_abi;
+using btknode::check_hip;
+using btknode::nstream;
+using btknode::d2h;
+using btknode::h2d;
+using btknode::even_pitch;
+using btknode::d2d_async;
 
 }  // namespace
 
@@ -97,7 +67,7 @@ void EnhancementBlockNode_::alloc_state_()
   const size_t n = state_bytes_();
   if (n) {
     init_state_(dState_.ensure(n));
-    d2d(dSnap_.ensure(n), dState_.get(), n);
+    d2d_async(dSnap_.ensure(n), dState_.get(), n);
   }
   state_ready_ = true;
 }
@@ -275,7 +245,7 @@ void EnhancementBlockNode_::ensure_current_()
   poll_sources_();
   if (!dirty_) return;
   const size_t n = state_bytes_();
-  if (n) d2d(dState_.get(), dSnap_.get(), n);
+  if (n) d2d_async(dState_.get(), dSnap_.get(), n);
   if (T_ > seg0_) launch_(dX_.get(), dY_.get(), Ts_, seg0_, T_, fd0_ + base_ + seg0_);
   dirty_ = false;
   Yhost_valid_ = false;
@@ -293,7 +263,7 @@ bool EnhancementBlockNode_::load_block_()
   const unsigned K = fftLen_ / 2 + 1;
   dY_.ensure(sizeof(float) * 2 * K * Ts_);
   const size_t n = state_bytes_();
-  if (n) d2d(dSnap_.get(), dState_.get(), n);
+  if (n) d2d_async(dSnap_.get(), dState_.get(), n);
   base_ = f0; T_ = Tn; seg0_ = 0;
   launch_(dX_.get(), dY_.get(), Ts_, 0, T_, fd0_ + base_);
   dirty_ = false; Yhost_valid_ = false; prepared_ = true;
@@ -308,7 +278,7 @@ void* EnhancementBlockNode_::begin_switch_(bool need_state)
   if (prepared_ && T_ > 0) {
     poll_sources_();
     const long n1 = std::min(std::max(handed_ + 1 - base_, seg0_), T_);
-    if (n) d2d(dState_.get(), dSnap_.get(), n);
+    if (n) d2d_async(dState_.get(), dSnap_.get(), n);
     if (n1 > seg0_) {
       // the frames between the segment's start and the mark once more, into a scratch block: what was handed over stays as it is
       const unsigned K = fftLen_ / 2 + 1;
@@ -329,8 +299,8 @@ void* EnhancementBlockNode_::begin_peek_()
   if (prepared_ && T_ > 0) {
     poll_sources_();
     const long n1 = std::min(std::max(handed_ + 1 - base_, seg0_), T_);
-    d2d(dPeek_.ensure(n), dState_.get(), n);
-    d2d(dState_.get(), dSnap_.get(), n);
+    d2d_async(dPeek_.ensure(n), dState_.get(), n);
+    d2d_async(dState_.get(), dSnap_.get(), n);
     if (n1 > seg0_) {
       const unsigned K = fftLen_ / 2 + 1;
       launch_(dX_.get(), dTmp_.ensure(sizeof(float) * 2 * K * Ts_), Ts_, seg0_, n1, fd0_ + base_ + seg0_);
@@ -342,14 +312,14 @@ void* EnhancementBlockNode_::begin_peek_()
 void EnhancementBlockNode_::end_peek_()
 {
   const size_t n = state_bytes_();
-  if (n && prepared_ && T_ > 0) d2d(dState_.get(), dPeek_.get(), n);
+  if (n && prepared_ && T_ > 0) d2d_async(dState_.get(), dPeek_.get(), n);
 }
 
 void EnhancementBlockNode_::end_switch_()
 {
   if (!state_ready_) return;
   const size_t n = state_bytes_();
-  if (n) d2d(dSnap_.get(), dState_.get(), n);
+  if (n) d2d_async(dSnap_.get(), dState_.get(), n);
 }
 
 const float* EnhancementBlockNode_::host_output_()
