@@ -210,6 +210,12 @@ SIGNATURES = {
     "btk_vad_simple_energy": (_i, [_vp, _l, _i, _l, _d, _d, _vp, _vp, _vp, _l, _vp]),
     "btk_vad_hangover": (_i, [_vp, _vp, _i, _i, _i, _l, _l, C.c_uint, C.c_uint, _i, _vp, _vp, _l, _vp, _i, _vp, _vp]),
     "btk_vad_gather": (_i, [_vp, _i, _l, _i, _l, _vp, _vp, _l, _vp, _vp]),
+    # objective measures (objective_measure/objective_measure.cc:42-185, :284-331)
+    "btk_obj_snr_workspace_bytes": (_l, [_i, _l]),
+    "btk_obj_snr": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "btk_obj_snr_db": (_f, [_d, _d]),
+    "btk_obj_is_tile_frames": (_i, [_vp]),
+    "btk_obj_is_distance": (_i, [_vp, _vp, _l, _vp, _l, _i, _vp, _vp, _l, _l, _vp, _vp, _vp, _l, _vp]),
 }
 
 

@@ -173,6 +173,7 @@ NormalizedEnergyMetric, TSPSVADMetric = _mod.NormalizedEnergyMetricPtr, _mod.TSP
 VAD, SimpleEnergyVAD = _mod.VADPtr, _mod.SimpleEnergyVADPtr
 HangoverVADFeature, HangoverMIVADFeature = _mod.HangoverVADFeaturePtr, _mod.HangoverMIVADFeaturePtr
 HangoverMultiStageVADFeature = _mod.HangoverMultiStageVADFeaturePtr
+SNR, ItakuraSaitoMeasurePS = _mod.SNRPtr, _mod.ItakuraSaitoMeasurePSPtr
 
 __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TYPE_APAB", "TYPE_ZELINSKI2", "NO_USE_POST_FILTER",
             "jarithmetic_error", "jinitialization_error", "jkey_error", "jparse_error", "jtype_error", "jiterator_error", "calc_all_delays",
@@ -185,4 +186,5 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "BinaryMaskFilter", "KimBinaryMaskFilter", "IIDBinaryMaskFilter", "KimITDThresholdEstimator", "IIDThresholdEstimator",
             "FDIIDThresholdEstimator",
             "SpectralPowerFloatFeature", "VADMetric", "EnergyVADMetric", "PowerSpectrumVADMetric", "NormalizedEnergyMetric", "TSPSVADMetric",
-            "VAD", "SimpleEnergyVAD", "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature"]
+            "VAD", "SimpleEnergyVAD", "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature",
+            "SNR", "ItakuraSaitoMeasurePS"]

@@ -17,6 +17,7 @@
 // The signs (-1)^k are folded into the float32 taps when the plan is made.
 #include "btk_internal.h"
 #include "fft_lds.h"
+#include "stft_tile.h"
 #include <cmath>
 #include <cstdint>
 #include <type_traits>
@@ -29,41 +30,9 @@ struct btk_prfb {
   float2* d_rot;     // [M2]   e^{-j pi i / M2} / M2: the analysis rotation with the inverse transform's factor
 };
 
-struct btk_stft {
-  int M, r, R, D, window_type;
-  float* d_win;      // [M]
-  float2* d_tw;      // [2*M] e^{+j pi j / M}
-};
-
 namespace {
 
-constexpr int NT = 256;                       // threads per workgroup (4 wavefronts)
-constexpr size_t LDS_MAX = 160 * 1024;
-
-// N-point complex transforms per workgroup tile: the FFT buffer stays at ~32 KB (two workgroups per CU at M2 = 512 and 1024 with
-// m = 4) and every pass of fft_lds tiles the workgroup
-template <int LOG2N> struct PrCfg {
-  static constexpr int N = 1 << LOG2N;
-  static constexpr int TT = N >= 64 ? 4096 / N : (N >= 16 ? 64 : 128);
-  static constexpr int STRIDE = N + 1;
-};
-
-// PCM span -> LDS: local index l <-> global sample g0 + l, zero outside [0, nsamples)
-__device__ __forceinline__ void stage_span(float* xs, const float* src, const float* pcm, long pcm_stride, long nsamples, long g0,
-                                           int span, int D, int tid)
-{
-  const bool vec_ok = ((pcm_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(pcm) & 15) == 0) && ((g0 & 3) == 0) &&
-                      ((D & 3) == 0) && ((span & 3) == 0);
-  if (vec_ok && g0 >= 0 && g0 + span <= nsamples) {
-    for (int l = tid * 4; l < span; l += NT * 4)
-      *reinterpret_cast<float4*>(xs + l) = *reinterpret_cast<const float4*>(src + g0 + l);
-  } else {
-    for (int l = tid; l < span; l += NT) {
-      const long g = g0 + l;
-      xs[l] = (g >= 0 && g < nsamples) ? src[g] : 0.0f;
-    }
-  }
-}
+// btk_stft, NT, LDS_MAX, PrCfg, stage_span and for_log2n are stft_tile.h's
 
 // XCD-aware mapping as in fb_kernels.hip: consecutive tiles of one channel share an XCD's L2 (PCM halo reuse)
 __device__ __forceinline__ bool tile_of_block(int ntiles, int nchan, int* chan, int* tile)
@@ -183,12 +152,7 @@ void stft_kernel(const float* __restrict__ pcm, long nsamples, long pcm_stride, 
   stage_span(xs, pcm + (long)chan * pcm_stride, pcm, pcm_stride, nsamples, g0, span, D, tid);
   __syncthreads();
 
-  for (int idx = tid; idx < TT * M; idx += NT) {
-    const int f = idx / M, i = idx % M;
-    zbuf[f * STRIDE + i] = make_float2(win[i] * xs[f * D + i], 0.0f);
-  }
-  __syncthreads();
-  fft_lds<LOG2N, TT, STRIDE, NT, -1>(zbuf, tw, tid);              // gsl_fft_complex_radix2_forward
+  stft_tile_spectra<LOG2N>(zbuf, tw, xs, win, D, tid);
   store_bins<M, TT, STRIDE>(zbuf, X, chan, N, T_stride, tt0, tcount, tid);
 }
 
@@ -386,23 +350,6 @@ int launch_stft(const btk_stft* fb, const float* pcm, long nsamples, long pcm_st
                      X, T_stride, t0, tcount, ntiles, nchan);
   BTK_HIP_CHECK(hipGetLastError());
   return BTK_OK;
-}
-
-// one launch per power of two: f(std::integral_constant<int, log2 n>), n in [lo, 2048]
-template <class F> int for_log2n(int n, int lo, F f)
-{
-  if (n >= lo) switch (n) {
-    case 8:    return f(std::integral_constant<int, 3>{});
-    case 16:   return f(std::integral_constant<int, 4>{});
-    case 32:   return f(std::integral_constant<int, 5>{});
-    case 64:   return f(std::integral_constant<int, 6>{});
-    case 128:  return f(std::integral_constant<int, 7>{});
-    case 256:  return f(std::integral_constant<int, 8>{});
-    case 512:  return f(std::integral_constant<int, 9>{});
-    case 1024: return f(std::integral_constant<int, 10>{});
-    case 2048: return f(std::integral_constant<int, 11>{});
-  }
-  return btk_set_error(BTK_ERR_PARAMETER, "unsupported transform length %d", n);
 }
 
 bool pow2_in(int n, int lo, int hi) { return n >= lo && n <= hi && (n & (n - 1)) == 0; }

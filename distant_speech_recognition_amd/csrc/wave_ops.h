@@ -52,6 +52,20 @@ template <class T> __device__ __forceinline__ T wave_sum(T v)
   return v;
 }
 __device__ __forceinline__ zd wave_sum(zd v) { return zmk(wave_sum(v.x), wave_sum(v.y)); }
+// the same butterfly over aligned groups of W lanes (W a power of two <= 64), in every lane of the group
+template <int W, class T> __device__ __forceinline__ T group_sum(T v)
+{
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// largest value over the 64 lanes, in every lane
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // value of a wavefront-uniform lane
 __device__ __forceinline__ double lane_d(double v, int lane)

@@ -2611,3 +2611,104 @@ class STFTBank(_FrameBank):
         self.D = M // self.R
         self._h = C.c_void_p()
         check(_lib.lib().btk_stft_create(C.byref(self._h), M, r, window_type))
+
+
+# ---------------------------------------------------------------------------- objective measures (obj_kernels.hip)
+SNR_MEAN, SNR_PEAK, SNR_POWER, SNR_PROJECT = 1, 2, 4, 8     # option bits of calcSNR (objective_measure.cc:42-185)
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def _obj_rows(x, name):
+    if x.dim() == 1:
+        x = x.unsqueeze(0)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s must be a float32 cuda tensor [S][samples] with contiguous rows" % name)
+    S, n = x.shape
+    stride = x.stride(0) if S > 1 else max(n, 1)
+    if stride < n:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: rows overlap" % name)
+    return x, S, n, stride
+
+
+def _obj_pair(x1, x2, n1, n2, name, nlow=1):
+    """Rows and lengths of a batch of pairs: x1, x2 float32 cuda [S][>= n]; n1, n2 host integers or sequences (default: the rows)."""
+    x1, S, L1, st1 = _obj_rows(x1, name + ": x1")
+    x2, S2, L2, st2 = _obj_rows(x2, name + ": x2")
+    if S != S2 or x1.device != x2.device:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: %d and %d signals" % (name, S, S2))
+    lens = []
+    for n, L in ((n1, L1), (n2, L2)):
+        a = np.full(S, L, np.int64) if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (S,)))
+        if a.min(initial=nlow) < nlow or a.max(initial=0) > L:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: lengths outside %d .. %d" % (name, nlow, L))
+        lens.append(a)
+    return x1, st1, x2, st2, S, lens[0], lens[1]
+
+
+def snr_db(sum_, err):
+    """calcSNR's last line on the host: err > 0 ? 10 log10f(float(sum / err)) : FLT_MAX -> float32."""
+    sum_, err = np.asarray(sum_, np.float64), np.asarray(err, np.float64)
+    f = _lib.lib().btk_obj_snr_db
+    return np.array([f(float(s), float(e)) for s, e in zip(sum_.ravel(), err.ravel())], np.float32).reshape(sum_.shape)
+
+
+def snr(x1, x2, n1=None, n2=None, option=0, segment=None):
+    """calcSNR for S pairs, x1 the clean and x2 the enhanced signals (float32 cuda [S][samples], inputs left as they are) ->
+    (snr float32 [S], stats float64 [S][6] = mu1, mu2, a1, a2, sum, err) on the host; with segment=L also the rows
+    sum_b, err_b float64 cuda [S][B][2] of the whole L-sample segments below min(n1, n2), B = max over the pairs (a pair's rows
+    beyond its own floor(nmin / L) are NaN)."""
+    x1, st1, x2, st2, S, n1, n2 = _obj_pair(x1, x2, n1, n2, "snr")
+    dev = x1.device
+    nmax = int(max(n1.max(), n2.max()))
+    ws = torch.empty(max(_lib.lib().btk_obj_snr_workspace_bytes(S, nmax), 8) // 8, dtype=torch.float64, device=dev)
+    stats = torch.empty((S, 6), dtype=torch.float64, device=dev)
+    seg, L, B = None, 0, 0
+    if segment is not None:
+        L = int(segment)
+        if L < 1:
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "snr: segment length %d" % L)
+        B = int((np.minimum(n1, n2) // L).max())
+        seg = torch.full((S, max(B, 1), 2), float("nan"), dtype=torch.float64, device=dev)
+    check(_lib.lib().btk_obj_snr(_ptr(x1), st1, _ptr(x2), st2, S, _np_ptr(n1), _np_ptr(n2), int(option), _ptr(stats), L,
+                                 _ptr(seg) if seg is not None else None, max(B, 1), _ptr(ws), _stream()))
+    st = stats.cpu().numpy()
+    out = (snr_db(st[:, 4], st[:, 5]), st)
+    return out + (seg[:, :B],) if seg is not None else out
+
+
+def segmental_snr(x1, x2, L, n1=None, n2=None, option=0, lo=-10.0, hi=35.0):
+    """The segmental SNR (this project's definition; the reference's segmentalSNR class is empty): mean over the B whole
+    segments of L samples below min(n1, n2) of 10 log10(sum_b / err_b) in float64 clamped to [lo, hi]; err_b = 0 gives hi,
+    sum_b = 0 gives lo, B = 0 gives NaN -> (float64 [S] on the host, the rows as snr(..., segment=L) returns them)."""
+    x1, st1, x2, st2, S, n1, n2 = _obj_pair(x1, x2, n1, n2, "segmental_snr")
+    _, _, seg = snr(x1, x2, n1, n2, option, segment=L)
+    rows = seg.cpu().numpy()
+    out = np.full(S, np.nan, np.float64)
+    for s in range(S):
+        B = int(min(n1[s], n2[s]) // int(L))
+        if B:
+            out[s] = segment_db(rows[s, :B, 0], rows[s, :B, 1], lo, hi).mean()
+    return out, seg
+
+
+def segment_db(sum_b, err_b, lo=-10.0, hi=35.0):
+    """10 log10(sum_b / err_b) in float64 clamped to [lo, hi]; err_b = 0 gives hi, else sum_b = 0 gives lo."""
+    sum_b, err_b = np.asarray(sum_b, np.float64), np.asarray(err_b, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.clip(10.0 * np.log10(sum_b / err_b), lo, hi)
+    v = np.where(sum_b == 0, lo, v)
+    return np.where(err_b == 0, hi, v)
+
+
+def is_distance(bank, x1, x2, n1=None, n2=None, bframe=0, eframe=-1, rows=False):
+    """calcISDistance over the frames of an STFTBank, fused with the transform: -> (distance float64 cuda [S], frames in range
+    int64 cuda [S]) and with rows=True also Eis float64 cuda [S][T], T = the largest min(F1, F2) (NaN beyond a pair's own)."""
+    x1, st1, x2, st2, S, n1, n2 = _obj_pair(x1, x2, n1, n2, "is_distance", nlow=0)
+    dev = x1.device
+    T = max(int(bank.num_frames(int(np.minimum(n1, n2).max()))), 1)
+    eis = torch.full((S, T), float("nan"), dtype=torch.float64, device=dev) if rows else torch.empty((S, T), dtype=torch.float64, device=dev)
+    dist = torch.empty(S, dtype=torch.float64, device=dev)
+    count = torch.empty(S, dtype=torch.int64, device=dev)
+    check(_lib.lib().btk_obj_is_distance(bank._h, _ptr(x1), st1, _ptr(x2), st2, S, _np_ptr(n1), _np_ptr(n2), int(bframe), int(eframe),
+                                         _ptr(dist), _ptr(count), _ptr(eis), T, _stream()))
+    return (dist, count, eis) if rows else (dist, count)

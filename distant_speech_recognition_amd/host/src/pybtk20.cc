@@ -1,6 +1,6 @@
 // pybtk20.cc -- Python binding of the C++ node layer (libbtk20hip.so): the classes the reference exposes through SWIG
 // (stream/stream.i, feature/feature.i, modulated/modulated.i, beamformer/beamformer.i, postfilter/postfilter.i,
-// dereverberation/dereverberation.i, convolution/convolution.i, sad/sad.i) bound with pybind11 under the same names.
+// dereverberation/dereverberation.i, convolution/convolution.i, sad/sad.i, objective_measure/objective_measure.i) bound with pybind11 under the same names.
 //   * a bound object IS the C++ node: the holder shares Countable's intrusive count with the refcountable_ptrs the nodes keep
 //     of each other, so Python and C++ references are one population;
 //   * next() returns a numpy VIEW of the node's vector_ (no copy; the array keeps the node alive) -- the reference's typemap
@@ -26,6 +26,7 @@
 #include "postfilter/spectralsubtraction.h"
 #include "postfilter/binauralprocessing.h"
 #include "sad/sad.h"
+#include "objective_measure/objective_measure.h"
 
 namespace py = pybind11;
 typedef std::complex<double> cd;
@@ -1218,4 +1219,31 @@ PYBIND11_MODULE(_btk20cpp, m)
            py::arg("metricPtr"), py::arg("threshold"))
       .def("setMetric", [as_metric](HangoverMultiStageVADFeature& f, py::object metricPtr, double threshold) { f.set_metric(as_metric(metricPtr), threshold); },
            py::arg("metricPtr"), py::arg("threshold"));
+
+  // ---- objective_measure/objective_measure.h (objective_measure/objective_measure.i)
+  py::class_<SNR, cref<SNR>>(m, "SNRPtr")
+      .def(py::init([]() { return new SNR(); }))
+      .def("getSNR", &SNR::getSNR, py::arg("fn1"), py::arg("fn2"), py::arg("normalizationOption"), py::arg("chX") = 1,
+           py::arg("samplerate") = 16000, py::arg("cfrom") = -1, py::arg("to") = -1)
+      .def("getSNR2", [](SNR& s, py::array_t<float, py::array::c_style | py::array::forcecast> original,
+                         py::array_t<float, py::array::c_style | py::array::forcecast> enhanced, int normalizationOption) {
+             gsl_vector_float a, b;
+             a.size = (size_t)original.size(); a.stride = 1; a.data = const_cast<float*>(original.data());
+             b.size = (size_t)enhanced.size(); b.stride = 1; b.data = const_cast<float*>(enhanced.data());
+             return s.getSNR2(&a, &b, normalizationOption);
+           }, py::arg("original"), py::arg("enhanced"), py::arg("normalizationOption"))
+      .def("stats", [](SNR& s) {
+             py::array_t<double> a(6);
+             std::copy(s.stats(), s.stats() + 6, a.mutable_data());
+             return a;
+           });
+  py::class_<ItakuraSaitoMeasurePS, cref<ItakuraSaitoMeasurePS>>(m, "ItakuraSaitoMeasurePSPtr")
+      .def(py::init([](unsigned fftLen, unsigned r, unsigned windowType, const std::string& nm) {
+             return new ItakuraSaitoMeasurePS(fftLen, r, windowType, nm);
+           }), py::arg("fftLen"), py::arg("r") = 1, py::arg("windowType") = 1, py::arg("nm") = "ItakuraSaitoMeasurePS")
+      .def("getDistance", &ItakuraSaitoMeasurePS::getDistance, py::arg("fn1"), py::arg("fn2"), py::arg("chX") = 1,
+           py::arg("samplerate") = 16000, py::arg("bframe") = 0, py::arg("eframe") = -1)
+      .def("frameShiftLength", &ItakuraSaitoMeasurePS::frameShiftLength)
+      .def("frames", &ItakuraSaitoMeasurePS::frames)
+      .def("distance", &ItakuraSaitoMeasurePS::distance);
 }

@@ -994,6 +994,43 @@ int  btk_vad_hangover(const double* const* values, const double* thresholds, int
 int  btk_vad_gather(const float* src, int S, long T, int D, long frame_base, const long long* hangover_state, float* dst,
                     long dst_rows, long long* count, void* stream);
 
+/* ---- Objective measures: objective_measure/objective_measure.cc -----------------------------------------------------------
+ * Arithmetic rule: element-wise values (centred and scaled samples, differences, bin powers, ratios) are the reference's float32;
+ * sums are float64 in an order fixed by the sample, bin or frame index alone: it depends neither on S, on a pair's place in the
+ * batch, on the strides, nor on which optional outputs are asked for.  No floating-point atomics.
+ *
+ * btk_obj_snr: calcSNR (:42-185) for S pairs.  x1, x2 [dev] float32 [S][stride]; n1, n2 [host] long [S], 1 <= n_c <= stride_c (the distance: 0 <= n_c);
+ *   nmin = min(n1, n2).  The inputs are not modified (the reference overwrites them).  option bits:
+ *     1  mu_c = f32((sum_{i<n_c} x_c[i]) / n_c), x_c[i] <- f32(x_c[i] - mu_c)                       (else mu_c = 0)
+ *   a1 = a2 = 1, then the first of
+ *     2  a_c = f32(1 / max(-10000, max_i x_c[i])): the signed maximum with the reference's initial value, not the peak
+ *     4  a2 = f32(sqrt((sum x1^2 / n1) / (sum x2^2 / n2)))
+ *     8  a2 = f32(sum_{i<n2} x1 x2 / sum_{i<n2} x2^2); needs n1 >= n2 (the reference reads past samp1): BTK_ERR_DIMENSION
+ *   v_c[i] = f32(x_c[i] a_c); sum = sum_{i<nmin} (double)v1^2, err = sum_{i<nmin} (double)f32(v1 - v2)^2, and the longer
+ *   signal's tail adds its v^2 to both (:159-176).  stats [dev] float64 [S][6] = mu1, mu2, a1, a2, sum, err; btk_obj_snr_db [host]
+ *   forms err > 0 ? 10 log10f(f32(sum / err)) : FLT_MAX of them, log10f correctly rounded (the float64 logarithm rounded once).
+ *   seg [dev] float64 [S][seg_stride][2] or NULL: sum_b, err_b of the whole segments of seg_len samples below nmin,
+ *   b < floor(nmin / seg_len) <= seg_stride (the rows behind a pair's last segment stay untouched).  The segmental SNR made of
+ *   them is this project's (the reference's segmentalSNR class is empty).
+ *   workspace [dev]: btk_obj_snr_workspace_bytes(S, max n) bytes, need not be initialised.
+ * btk_obj_is_distance: calcISDistance (:284-331) for S pairs over the frames of a btk_stft plan, the bits btk_stft_analysis
+ *   gives: F = min(btk_stft_num_frames(n1), btk_stft_num_frames(n2)); per frame and bin kappa = 1 .. M/2
+ *     P_c = f32((double)re^2 + (double)im^2); P1 > 0 and P2 > 0: ratio = f32(P1 / P2), term = (double)ratio - log(ratio) - 1,
+ *     else term = 0;  Eis_t = (sum_kappa term) / (M/2)  (skipped bins stay in the divisor)
+ *   dist [dev] float64 [S] = mean of Eis_t over bframe <= t < F and t <= eframe unless eframe < 0, NaN where no frame is in
+ *   range; count [dev] int64 [S] frames in range; eis [dev] float64 [S][e_stride], e_stride >= F: the rows t < F (always
+ *   written: the mean is taken from them).  btk_obj_is_tile_frames: frames a workgroup transforms at this plan's M.
+ * BTK_ERR_DIMENSION for a bad size or length, BTK_ERR_PARAMETER for a null pointer or unknown option bits; nothing is launched
+ * and the outputs stay untouched.                                                                                            */
+long btk_obj_snr_workspace_bytes(int S, long nmax);
+int  btk_obj_snr(const float* x1, long stride1, const float* x2, long stride2, int S, const long* n1, const long* n2, int option,
+                 double* stats, long seg_len, double* seg, long seg_stride, void* workspace, void* stream);
+float btk_obj_snr_db(double sum, double err);
+int  btk_obj_is_tile_frames(const btk_stft_t* fb);
+int  btk_obj_is_distance(const btk_stft_t* fb, const float* x1, long stride1, const float* x2, long stride2, int S,
+                         const long* n1, const long* n2, long bframe, long eframe, double* dist, long long* count, double* eis,
+                         long e_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
