@@ -9,7 +9,8 @@ import sys
 from distant_speech_recognition_amd.btk20 import *      # noqa: F401,F403
 from distant_speech_recognition_amd.btk20 import __all__  # noqa: F401
 
-for _name in ("stream", "feature", "modulated", "beamformer", "postfilter", "dereverberation", "aec", "common", "convolution", "sad", "objective_measure"):
+for _name in ("stream", "feature", "modulated", "beamformer", "postfilter", "dereverberation", "aec", "common", "convolution", "sad", "objective_measure",
+              "localization"):
     _mod = importlib.import_module("distant_speech_recognition_amd.btk20." + _name)
     sys.modules[__name__ + "." + _name] = _mod
     globals()[_name] = _mod

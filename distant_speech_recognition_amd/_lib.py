@@ -216,6 +216,13 @@ SIGNATURES = {
     "btk_obj_snr_db": (_f, [_d, _d]),
     "btk_obj_is_tile_frames": (_i, [_vp]),
     "btk_obj_is_distance": (_i, [_vp, _vp, _l, _vp, _l, _i, _vp, _vp, _l, _l, _vp, _vp, _vp, _l, _vp]),
+    # multichannel cross-correlation localisation (localization/mcc_localizer.cc:54-161, :322-451; localization.cc:107-118)
+    "btk_mcc_max_sample_delay": (_l, [C.c_uint, _f]),
+    "btk_mcc_sample_delays": (_i, [C.c_uint, _i, _vp, _vp]),
+    "btk_mcc_linear_grid": (_i, [C.c_uint, _i, _vp, _f, _i, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp]),
+    "btk_mcc_cost": (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "btk_mcc_select": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp]),
+    "btk_mcc_matrices": (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
 }
 
 

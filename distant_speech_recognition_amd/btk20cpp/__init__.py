@@ -174,6 +174,8 @@ VAD, SimpleEnergyVAD = _mod.VADPtr, _mod.SimpleEnergyVADPtr
 HangoverVADFeature, HangoverMIVADFeature = _mod.HangoverVADFeaturePtr, _mod.HangoverMIVADFeaturePtr
 HangoverMultiStageVADFeature = _mod.HangoverMultiStageVADFeaturePtr
 SNR, ItakuraSaitoMeasurePS = _mod.SNRPtr, _mod.ItakuraSaitoMeasurePSPtr
+SearchGridBuilder, SGB4LinearArray = _mod.SearchGridBuilderPtr, _mod.SGB4LinearArrayPtr
+MCCLocalizer, MCCCalculator = _mod.MCCLocalizerPtr, _mod.MCCCalculatorPtr
 
 __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TYPE_APAB", "TYPE_ZELINSKI2", "NO_USE_POST_FILTER",
             "jarithmetic_error", "jinitialization_error", "jkey_error", "jparse_error", "jtype_error", "jiterator_error", "calc_all_delays",
@@ -187,4 +189,4 @@ __all__ += ["device", "SSPEED", "TYPE_ZELINSKI1_REAL", "TYPE_ZELINSKI1_ABS", "TY
             "FDIIDThresholdEstimator",
             "SpectralPowerFloatFeature", "VADMetric", "EnergyVADMetric", "PowerSpectrumVADMetric", "NormalizedEnergyMetric", "TSPSVADMetric",
             "VAD", "SimpleEnergyVAD", "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature",
-            "SNR", "ItakuraSaitoMeasurePS"]
+            "SNR", "ItakuraSaitoMeasurePS", "SearchGridBuilder", "SGB4LinearArray", "MCCLocalizer", "MCCCalculator"]

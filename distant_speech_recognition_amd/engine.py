@@ -2712,3 +2712,129 @@ def is_distance(bank, x1, x2, n1=None, n2=None, bframe=0, eframe=-1, rows=False)
     check(_lib.lib().btk_obj_is_distance(bank._h, _ptr(x1), st1, _ptr(x2), st2, S, _np_ptr(n1), _np_ptr(n2), int(bframe), int(eframe),
                                          _ptr(dist), _ptr(count), _ptr(eis), T, _stream()))
     return (dist, count, eis) if rows else (dist, count)
+
+
+# ---------------------------------------------------------------------------- multichannel cross-correlation localisation
+MCC_RESET_COST = 100000.0            # the cost an N-best entry starts with (mcc_localizer.h:155); its index is -1
+MCC_MAX_NBEST = 16
+
+
+def mcc_max_sample_delay(fs, max_time_delay):
+    """D = (size_t)(fs * maxTimeDelay), the float product of mcc_localizer.cc:273."""
+    return int(_lib.lib().btk_mcc_max_sample_delay(int(fs), float(max_time_delay)))
+
+
+def mcc_sample_delays(fs, delays):
+    """tau = (int)(float)(fs * delay) per channel (mcc_localizer.cc:333-335): delays float64 [..., N] seconds -> int32."""
+    d = np.ascontiguousarray(delays, np.float64)
+    tau = np.zeros(d.shape, np.int32)
+    if d.size:
+        check(_lib.lib().btk_mcc_sample_delays(int(fs), d.size, _np_ptr(d), _np_ptr(tau)))
+    return tau
+
+
+def mcc_linear_grid(fs, N, spacing=None, positions=None):
+    """The far-field walk of SGB4LinearArray (mcc_localizer.cc:54-161) for N microphones `spacing` mm apart or at `positions`
+    (mm, [N][3], or [N] along the array's y axis) -> dict(azimuths float64 [G], delays float64 [G][N], tau int32 [G][N],
+    D, max_time_delay, const_v)."""
+    L = _lib.lib()
+    pos = None
+    if positions is not None:
+        pos = np.asarray(positions, np.float64)
+        if pos.ndim == 1:
+            pos = np.stack([np.zeros_like(pos), pos, np.zeros_like(pos)], axis=1)
+        pos = np.ascontiguousarray(pos)
+        if pos.shape != (N, 3):
+            raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "The size of the matrix for the geometry of the array should be %d x 3" % N)
+    elif spacing is None:
+        raise _lib.BtkError(_lib.BTK_ERR_PARAMETER, "mcc_linear_grid: give spacing or positions")
+    args = (int(fs), int(N), _np_ptr(pos) if pos is not None else None, float(spacing or 0.0))
+    n, mtd, cv = C.c_int(0), C.c_float(0), C.c_float(0)
+    check(L.btk_mcc_linear_grid(*args, 0, C.byref(n), C.byref(mtd), C.byref(cv), None, None, None))
+    G = n.value
+    az, dl, tau = np.zeros(G, np.float64), np.zeros((G, N), np.float64), np.zeros((G, N), np.int32)
+    check(L.btk_mcc_linear_grid(*args, G, C.byref(n), C.byref(mtd), C.byref(cv), _np_ptr(az), _np_ptr(dl), _np_ptr(tau)))
+    return dict(azimuths=az, delays=dl, tau=tau, D=mcc_max_sample_delay(fs, mtd.value), max_time_delay=mtd.value, const_v=cv.value)
+
+
+def _mcc_args(x, tau, L, name):
+    if x.dim() == 2:
+        x = x[None]
+    _check(x, "x", torch.float32, 3)
+    S, N, n = (int(v) for v in x.shape)
+    tau = np.ascontiguousarray(tau.cpu().numpy() if isinstance(tau, torch.Tensor) else tau)
+    if tau.ndim == 1:
+        tau = tau[None]
+    if tau.ndim != 2 or tau.shape[1] != N or not np.issubdtype(tau.dtype, np.integer):
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "%s: tau must be an integer array [G][%d], got %s %s" % (name, N, tau.dtype, tau.shape))
+    tau = np.ascontiguousarray(tau, np.int32)
+    L = int(L)
+    B = n // L if L > 0 else 0
+    tau_dev = torch.empty(tau.shape, dtype=torch.int32, device=x.device)
+    return x, S, N, n, B, L, tau, tau_dev
+
+
+def mcc_costs(x, tau, L, D, normalize_variance=True):
+    """The MCC objective of every block and candidate (calcCovarianceMatrix + calcObjectiveFunction, mcc_localizer.cc:322-411).
+    x float32 cuda [S][N][samples] (or [N][samples]) cut into B = samples // L blocks, tau int [G][N] sample delays, |tau| <= D
+    -> (cost float64 [S][B][G], flag uint8 [S][B][G]); flag 1 and cost 0.0 where R is not positive definite or a channel is dead."""
+    x, S, N, n, B, L, tau, tau_dev = _mcc_args(x, tau, L, "mcc_costs")
+    G = tau.shape[0]
+    cost = torch.empty((S, max(B, 0), G), dtype=torch.float64, device=x.device)
+    flag = torch.empty((S, max(B, 0), G), dtype=torch.uint8, device=x.device)
+    check(_lib.lib().btk_mcc_cost(_ptr(x), n, S, N, B, L, int(D), _np_ptr(tau), _ptr(tau_dev), G, 1 if normalize_variance else 0,
+                                  _ptr(cost), _ptr(flag), _stream()))
+    return cost, flag
+
+
+def mcc_select(cost, nbest=1):
+    """The N-best insertion of MCCLocalizer::search (mcc_localizer.cc:431-443) over the last axis of cost (float64 cuda
+    [...][G]), in grid order with strict < -> (nbest_cost float64 [...][nbest], nbest_idx int32 [...][nbest]); entries nothing
+    was inserted into keep (MCC_RESET_COST, -1)."""
+    _need_cuda(cost, "cost")
+    if cost.dtype != torch.float64 or cost.dim() < 1:
+        raise _lib.BtkError(_lib.BTK_ERR_DIMENSION, "cost must be float64 [...][G]")
+    G = int(cost.shape[-1])
+    SB = int(cost.numel() // max(G, 1))
+    nbest = int(nbest)
+    shape = tuple(cost.shape[:-1]) + (max(nbest, 0),)
+    nb_cost = torch.empty(shape, dtype=torch.float64, device=cost.device)
+    nb_idx = torch.empty(shape, dtype=torch.int32, device=cost.device)
+    check(_lib.lib().btk_mcc_select(_ptr(cost), SB, G, nbest, _ptr(nb_cost), _ptr(nb_idx), _stream()))
+    return nb_cost, nb_idx
+
+
+def mcc_matrices(x, tau, L, D, pairs):
+    """R float64 cuda [P][N][N] of the (block, candidate) pairs in `pairs` (int [P][2]: s B + b, g): the sums mcc_costs works
+    from, bit for bit, both triangles."""
+    x, S, N, n, B, L, tau, tau_dev = _mcc_args(x, tau, L, "mcc_matrices")
+    pairs = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    P = pairs.shape[0]
+    pairs_dev = torch.empty((max(P, 1), 2), dtype=torch.int32, device=x.device)
+    R = torch.empty((P, N, N), dtype=torch.float64, device=x.device)
+    check(_lib.lib().btk_mcc_matrices(_ptr(x), n, S, N, B, L, int(D), _np_ptr(tau), _ptr(tau_dev), tau.shape[0], _np_ptr(pairs),
+                                      _ptr(pairs_dev), P, _ptr(R), _stream()))
+    return R
+
+
+def mcc_localize(x, tau, L, D, nbest=1, want_matrices=False):
+    """MCCLocalizer::search for every block: costs of all candidates, then the N-best list -> dict with cost float64
+    [S][B][G], flag uint8 [S][B][G], nbest_cost float64 [S][B][nbest], nbest_idx int32 [S][B][nbest] and, with
+    want_matrices, R_best float64 [S][B][nbest][N][N] (NaN where the list entry is empty) and R_last float64 [S][B][N][N], the
+    matrix of the last grid candidate (what getR() holds after next()).  Asking for the matrices waits for the indices."""
+    cost, flag = mcc_costs(x, tau, L, D, True)
+    nb_cost, nb_idx = mcc_select(cost, nbest)
+    out = dict(cost=cost, flag=flag, nbest_cost=nb_cost, nbest_idx=nb_idx)
+    if want_matrices:
+        S, B, G = cost.shape
+        N = x.shape[-2]
+        idx = nb_idx.cpu().numpy().reshape(S * B, -1)
+        pairs = np.zeros((S * B, idx.shape[1] + 1, 2), np.int32)
+        pairs[:, :, 0] = np.arange(S * B)[:, None]
+        pairs[:, :-1, 1] = np.maximum(idx, 0)
+        pairs[:, -1, 1] = G - 1
+        R = mcc_matrices(x, tau, L, D, pairs).reshape(S, B, idx.shape[1] + 1, N, N)
+        Rb = R[:, :, :-1].clone()
+        Rb[torch.from_numpy(idx.reshape(S, B, -1) < 0).to(Rb.device)] = float("nan")
+        out["R_best"], out["R_last"] = Rb, R[:, :, -1].contiguous()
+    return out

@@ -1,6 +1,7 @@
 // pybtk20.cc -- Python binding of the C++ node layer (libbtk20hip.so): the classes the reference exposes through SWIG
 // (stream/stream.i, feature/feature.i, modulated/modulated.i, beamformer/beamformer.i, postfilter/postfilter.i,
-// dereverberation/dereverberation.i, convolution/convolution.i, sad/sad.i, objective_measure/objective_measure.i) bound with pybind11 under the same names.
+// dereverberation/dereverberation.i, convolution/convolution.i, sad/sad.i, objective_measure/objective_measure.i,
+// localization/localization.i:128-260) bound with pybind11 under the same names.
 //   * a bound object IS the C++ node: the holder shares Countable's intrusive count with the refcountable_ptrs the nodes keep
 //     of each other, so Python and C++ references are one population;
 //   * next() returns a numpy VIEW of the node's vector_ (no copy; the array keeps the node alive) -- the reference's typemap
@@ -27,6 +28,7 @@
 #include "postfilter/binauralprocessing.h"
 #include "sad/sad.h"
 #include "objective_measure/objective_measure.h"
+#include "localization/localization.h"
 
 namespace py = pybind11;
 typedef std::complex<double> cd;
@@ -1246,4 +1248,60 @@ PYBIND11_MODULE(_btk20cpp, m)
       .def("frameShiftLength", &ItakuraSaitoMeasurePS::frameShiftLength)
       .def("frames", &ItakuraSaitoMeasurePS::frames)
       .def("distance", &ItakuraSaitoMeasurePS::distance);
+
+  // ---- localization/localization.h (localization/localization.i:128-260)
+  auto as_sgb = [](py::object o) { return SearchGridBuilderPtr(o.cast<SearchGridBuilder*>()); };
+  py::class_<SearchGridBuilder, cref<SearchGridBuilder>>(m, "SearchGridBuilderPtr")
+      .def(py::init([](int nChan, bool isFarField, unsigned int samplingFreq) { return new SearchGridBuilder(nChan, isFarField, samplingFreq); }),
+           py::arg("nChan"), py::arg("isFarField"), py::arg("samplingFreq") = 16000u)
+      .def("nextSearchGrid", [](SearchGridBuilder& g) { return g.nextSearchGrid(); })
+      .def("getTimeDelays", [](py::object self) -> py::object {
+             const gsl_vector* v = self.cast<SearchGridBuilder&>().getTimeDelays();
+             if (!v) return py::none();
+             return view(v, self); })
+      .def("getSearchPosition", [](py::object self) { return view(self.cast<SearchGridBuilder&>().getSearchPosition(), self); })
+      .def("maxTimeDelay", [](SearchGridBuilder& g) { return g.maxTimeDelay(); })
+      .def("chanN", [](SearchGridBuilder& g) { return g.chanN(); })
+      .def("samplingFrequency", [](SearchGridBuilder& g) { return g.samplingFrequency(); })
+      .def("reset", [](SearchGridBuilder& g) { g.reset(); });
+  py::class_<SGB4LinearArray, SearchGridBuilder, cref<SGB4LinearArray>>(m, "SGB4LinearArrayPtr")
+      .def(py::init([](int nChan, bool isFarField, unsigned int samplingFreq) { return new SGB4LinearArray(nChan, isFarField, samplingFreq); }),
+           py::arg("nChan"), py::arg("isFarField"), py::arg("samplingFreq") = 16000u)
+      .def("setDistanceBtwMicrophones", [](SGB4LinearArray& g, float distance) { g.setDistanceBtwMicrophones(distance); }, py::arg("distance"))
+      .def("setPositionsOfMicrophones", [](SGB4LinearArray& g, py::array_t<double, py::array::c_style | py::array::forcecast> mpos) {
+             GslMat mp(mpos);
+             g.setPositionsOfMicrophones(mp.m);
+           }, py::arg("mpos"));
+  py::class_<MCCLocalizer, VectorFeatureStream, cref<MCCLocalizer>>(m, "MCCLocalizerPtr")
+      .def(py::init([as_sgb](py::object sgbPtr, size_t maxSource, const std::string& nm) {
+             SearchGridBuilderPtr g = as_sgb(sgbPtr);
+             return new MCCLocalizer(g, maxSource, nm);
+           }), py::arg("sgbPtr"), py::arg("maxSource") = 1, py::arg("nm") = "MCCSourceLocalizer")
+      .def("reset", [](MCCLocalizer& l) { l.reset(); })
+      .def("setChannel", [](MCCLocalizer& l, py::object chan) { VectorFloatFeatureStreamPtr c = as_fstream(chan); l.setChannel(c); }, py::arg("chan"))
+      .def("getDelayedSample", [](MCCLocalizer& l, int chanX) { return l.getDelayedSample(chanX); }, py::arg("chanX"))
+      .def("getMaxMCCC", [](MCCLocalizer& l) { return l.getMaxMCCC(); })
+      .def("getPosition", [](py::object self) { return view(self.cast<MCCLocalizer&>().getPosition(), self); })
+      .def("getNthBestDelayedSample", [](MCCLocalizer& l, int nth, int chanX) { return l.getNthBestDelayedSample(nth, chanX); }, py::arg("nth"), py::arg("chanX"))
+      .def("getNthBestMCCC", [](MCCLocalizer& l, int nth) { return l.getNthBestMCCC(nth); }, py::arg("nth"))
+      .def("getNthBestPosition", [](py::object self, int nth) { return view(self.cast<MCCLocalizer&>().getNthBestPosition(nth), self); }, py::arg("nth"))
+      .def("getEigenValues", [](py::object self) { return view(self.cast<MCCLocalizer&>().getEigenValues(), self); })
+      .def("getR", [](MCCLocalizer& l) { return dense_of(l.getR()); })
+      .def("set_block_frames", [](MCCLocalizer& l, long n) { l.set_block_frames(n); }, py::arg("n"))
+      .def("block_frames", [](MCCLocalizer& l) { return l.block_frames(); })
+      .def("launches", [](MCCLocalizer& l) { return l.launches(); });
+  py::class_<MCCCalculator, MCCLocalizer, cref<MCCCalculator>>(m, "MCCCalculatorPtr")
+      .def(py::init([as_sgb](py::object sgbPtr, bool normalizeVariance, const std::string& nm) {
+             SearchGridBuilderPtr g = as_sgb(sgbPtr);
+             return new MCCCalculator(g, normalizeVariance, nm);
+           }), py::arg("sgbPtr"), py::arg("normalizeVariance") = true, py::arg("nm") = "MCCCalculator")
+      .def("reset", [](MCCCalculator& l) { l.reset(); })
+      .def("setTimeDelays", [](MCCCalculator& l, py::array_t<double, py::array::c_style | py::array::forcecast> delays) {
+             GslVec d(delays);
+             l.setTimeDelays(d.v);
+           }, py::arg("delays"))
+      .def("getMCCC", [](MCCCalculator& l) { return l.getMCCC(); })
+      .def("getCostV", [](MCCCalculator& l) { return l.getCostV(); })
+      .def("normalizeVariance", [](MCCCalculator& l) { return l.normalizeVariance(); })
+      .def("setNormalizeVariance", [](MCCCalculator& l, bool v) { l.setNormalizeVariance(v); }, py::arg("normalizeVariance"));
 }

@@ -1031,6 +1031,45 @@ int  btk_obj_is_distance(const btk_stft_t* fb, const float* x1, long stride1, co
                          const long* n1, const long* n2, long bframe, long eframe, double* dist, long long* count, double* eis,
                          long e_stride, void* stream);
 
+/* ---- Multichannel cross-correlation localisation: SearchGridBuilder / SGB4LinearArray / MCCLocalizer / MCCCalculator
+ * (localization/mcc_localizer.h:36-78, :153-260; mcc_localizer.cc) -----------------------------------------------------------
+ * Host helpers (no device needed), the reference's types as written:
+ * btk_mcc_max_sample_delay: D = (size_t)(fs * maxTimeDelay), a float product (mcc_localizer.cc:273, :326).
+ * btk_mcc_sample_delays: tau[c] = (int)(float)(fs * delays[c]), the double product rounded to float and truncated toward zero
+ *   (:333-335); delays [host] float64 [n] seconds, tau_out [host] int32 [n].
+ * btk_mcc_linear_grid: the far-field walk of SGB4LinearArray (:54-161): positions [host] float64 [N][3] in mm
+ *   (setPositionsOfMicrophones; microphone 0 is copied and is pos0, which the reference's loop from 1 never does), or NULL and
+ *   `distance` in mm (setDistanceBtwMicrophones).  The walk starts at azimuth 0, goes in steps of _constV in sin(azimuth) up to
+ *   pi/2, jumps to 3 pi/2 and ends just below 2 pi.  n_points: the number of grid points; max_time_delay, const_v (may be NULL):
+ *   _maxTimeDelay, _constV.  azimuths [host] float64 [max_points], delays [host] float64 [max_points][N]
+ *   (calcDelaysOfLinearMicrophoneArray, localization.cc:107-118, 343740 mm/s), tau [host] int32 [max_points][N]: each may be
+ *   NULL; all NULL counts only.  More points than max_points (or than 4096): BTK_ERR_DIMENSION.
+ * Device entry points.  x [dev] float32 [S][N][len]: S streams of N channels, cut into B blocks of L samples from sample 0
+ * (B L <= len).  tau_host [host] int32 [G][N] is checked (|tau| <= D) and copied to tau_dev [dev] int32 [G][N] on the stream.
+ * btk_mcc_cost: calcCovarianceMatrix + calcObjectiveFunction (:322-411) of every (stream, block, candidate):
+ *     R = (1 / nS) sum_{f < nS} xt[f] xt[f]^T in float64, nS = L - D, xt_c[f] = x_c[f + tau_c], or x_c[L + f + tau_c] where
+ *     f + tau_c < 0 (SampleHolder holds the CURRENT block's last D samples, :336: no state crosses a block boundary)
+ *     cost [dev] float64 [S][B][G] = sum log d_j - (normalize_variance ? sum log R_ii : 0), d_j the pivots of R = L diag(d) L^T
+ *     flag [dev] uint8 [S][B][G] = 1 and cost = 0.0 where a pivot or an R_ii is not > 0 (the zero-eigenvalue branch, :386-397;
+ *     the reference takes |lambda| of a negative eigenvalue instead, which an exact Gram matrix has from rounding only)
+ *   The summation order depends on (N, L, D) alone: equal tau rows give equal bits, whatever else is in the launch.
+ * btk_mcc_select: the N-best insertion of search() (:431-443) in grid order, strict <, every entry starts at cost 100000:
+ *   cost [dev] float64 [SB][G] -> nbest_cost [dev] float64 [SB][nbest], nbest_idx [dev] int32 [SB][nbest] (-1 where nothing
+ *   was inserted).  nbest = maxSource <= 16.
+ * btk_mcc_matrices: R [dev] float64 [P][N][N] (both triangles) of the P pairs (s B + b, g) in pairs_host [host] int32 [P][2],
+ *   copied to pairs_dev [dev] int32 [P][2]; the sums of btk_mcc_cost, bit for bit.
+ * BTK_ERR_DIMENSION unless 2 <= N <= 64, 1 <= G <= 4096, 2 D <= L <= 65536 ("Data samples are insufficient", :329),
+ * |tau| <= D (the reference would read outside its buffers), 1 <= nbest <= 16; nothing is launched then.                    */
+long btk_mcc_max_sample_delay(unsigned int fs, float max_time_delay);
+int  btk_mcc_sample_delays(unsigned int fs, int n, const double* delays, int* tau_out);
+int  btk_mcc_linear_grid(unsigned int fs, int N, const double* positions, float distance, int max_points, int* n_points,
+                         float* max_time_delay, float* const_v, double* azimuths, double* delays, int* tau);
+int  btk_mcc_cost(const void* x, long len, int S, int N, int B, int L, int D, const int* tau_host, void* tau_dev, int G,
+                  int normalize_variance, void* cost, void* flag, void* stream);
+int  btk_mcc_select(const void* cost, long SB, int G, int nbest, void* nbest_cost, void* nbest_idx, void* stream);
+int  btk_mcc_matrices(const void* x, long len, int S, int N, int B, int L, int D, const int* tau_host, void* tau_dev, int G,
+                      const int* pairs_host, void* pairs_dev, int P, void* R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ import sys
 
 REF = "/root/reference/btk20_src"
 FILES = ["feature/feature.i", "modulated/modulated.i", "beamformer/beamformer.i", "postfilter/postfilter.i",
-         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i", "convolution/convolution.i", "sad/sad.i", "objective_measure/objective_measure.i"]
+         "dereverberation/dereverberation.i", "stream/stream.i", "aec/aec.i", "convolution/convolution.i", "sad/sad.i", "objective_measure/objective_measure.i",
+         "localization/localization.i"]
 CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature", "SpectralPowerFeature", "VTLNFeature", "MelFeature",
            "LogFeature", "CepstralFeature", "StorageFeature", "OverSampledDFTAnalysisBank", "OverSampledDFTSynthesisBank", "SnapShotArray", "SpectralMatrixArray",
            "SubbandBeamformer", "SubbandDS", "SubbandGSC", "SubbandGSCRLS", "SubbandMVDR", "SubbandMVDRGSC", "ZelinskiPostFilter",
@@ -25,7 +26,8 @@ CLASSES = ["SampleFeature", "HammingFeature", "FFTFeature", "PreemphasisFeature"
            "DelayFeature", "BinaryMaskFilter", "KimBinaryMaskFilter", "KimITDThresholdEstimator", "IIDBinaryMaskFilter",
            "IIDThresholdEstimator", "FDIIDThresholdEstimator", "SpectralPowerFloatFeature", "VADMetric", "EnergyVADMetric",
            "FloatMultiChannelVADMetric", "PowerSpectrumVADMetric", "NormalizedEnergyMetric", "TSPSVADMetric", "VAD", "SimpleEnergyVAD",
-           "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature", "SNR", "ItakuraSaitoMeasurePS"]
+           "HangoverVADFeature", "HangoverMIVADFeature", "HangoverMultiStageVADFeature", "SNR", "ItakuraSaitoMeasurePS",
+           "SearchGridBuilder", "SGB4LinearArray", "MCCLocalizer", "MCCCalculator"]
 SKIP = {"next", "reset", "is_end", "isEnd", "size", "frame_no", "operator->", "__iter__", "name", "current",
         # the log-file functions of VADMetric (_LOG_SAD_) are not carried over
         "openLogFile", "writeLog", "closeLogFile", "initScore", "setScore", "getAverageScore", "initScores", "getScores"}
