@@ -33,7 +33,8 @@ def problem(K, N, T, dev, seed=1):
     noise = 0.3 * (rng.normal(size=(K, N, T)) + 1j * rng.normal(size=(K, N, T)))
     X = (a_t[:, :, None] * s + a_j[:, :, None] * j + noise).astype(np.complex64)
     wuH = (np.conjugate(a_t) / N)[None]                                     # [1][K][N]
-    BmH = np.stack([eng.weights_blocking_matrix(np.conjugate(wuH[0, kk]), 1).T for kk in range(K)])[None]
+    # a stack of transposes comes out in the transposes' memory order: hos_eval wants the rows of BmH contiguous
+    BmH = np.ascontiguousarray(np.stack([eng.weights_blocking_matrix(np.conjugate(wuH[0, kk]), 1).T for kk in range(K)])[None])
     pw = np.mean(np.abs(np.einsum("kn,knt->kt", wuH[0], X[:, :, :256])) ** 2)
     X = (X / np.sqrt(pw)).astype(np.complex64)
     return torch.from_numpy(X).to(dev), torch.from_numpy(wuH).to(dev), torch.from_numpy(BmH).to(dev)

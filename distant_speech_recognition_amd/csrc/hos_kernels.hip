@@ -17,6 +17,8 @@
 //   phase 2  (gradient only) wavefront w owns the channels w, w + 8, ...: each lane multiplies 8 frames of the tile into its own
 //            partial sums of the two N-vectors -- 8 channels x 2 vectors complex float64 accumulators per lane, statically indexed.
 //            With two sources the frames are passed over once per source: both sources' sums do not fit beside the loads.
+//            The samples of a frame that is not selected are never read here (its lane reads the first selected frame against
+//            its zero coefficients): the reference never touches such a frame, whatever it holds.
 // Lane partials are combined by an xor butterfly, wavefront partials in wavefront order by one lane: a fixed order, no atomics,
 // so two runs give the same bits.  hos_minimize_kernel runs the whole Polak-Ribiere+ / Armijo iteration of a bin inside its
 // workgroup: the vectors of the optimiser live in LDS, every decision is taken by lane 0 and broadcast through LDS.
@@ -66,23 +68,37 @@ struct hos_lds {
   double x[HOS_MAXD], g[HOS_MAXD], d[HOS_MAXD], xt[HOS_MAXD];
   double sc[4];
   int flag;
+  // phase 2 reads a frame that is not selected at the first selected one
+  long long tfirst;
+  long long first[HOS_WAVES];
+  long long src[HOS_TILE];                   // the frame phase 2 reads for each frame of the tile: itself if it is selected
 };
 
-// number of selected frames of the block (the reference's len(self._observations))
+// number of selected frames of the block (the reference's len(self._observations)) and the first of them (0 if there is none)
 template <int NS>
 __device__ void hos_count_frames(const hos_args& a, hos_lds<NS>& L)
 {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int c = 0;
-  for (long t = tid; t < a.T; t += HOS_THREADS) c += (!a.mask || a.mask[t] != 0.f) ? 1 : 0;
+  long long first = a.T;
+  for (long t = tid; t < a.T; t += HOS_THREADS) {
+    const bool s = !a.mask || a.mask[t] != 0.f;
+    c += s ? 1 : 0;
+    first = s && t < first ? t : first;
+  }
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-  if (lane == 0) L.cnt[wave] = c;
+  for (int m = 32; m >= 1; m >>= 1) {
+    c += __shfl_xor(c, m);
+    const long long o = __shfl_xor(first, m);
+    first = o < first ? o : first;
+  }
+  if (lane == 0) { L.cnt[wave] = c; L.first[wave] = first; }
   __syncthreads();
   if (tid == 0) {
-    long long n = 0;
-    for (int w = 0; w < HOS_WAVES; w++) n += L.cnt[w];
+    long long n = 0, f = a.T;
+    for (int w = 0; w < HOS_WAVES; w++) { n += L.cnt[w]; f = L.first[w] < f ? L.first[w] : f; }
     L.tsel = n;
+    L.tfirst = f < a.T ? f : 0;
   }
   __syncthreads();
 }
@@ -210,6 +226,7 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
         }
         m /= (double)NS;
         if (sp == 0) { m2 += m; m4 += m * m; }
+        if (want_grad) L.src[tid] = sel ? t : L.tfirst;
       }
       // ---- phase 2: an objective-only pass (every line-search trial) has none, and no barrier in its tile loop
       if (want_grad) {
@@ -217,8 +234,11 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
 #pragma unroll
         for (int j = 0; j < HOS_FPL; j++) {
           const int tt = lane + 64 * j;
-          const long t = t0 + tt;
-          const float2* xt = Xk + (t < a.T ? t : a.T - 1); // beyond T the coefficients in LDS are zero: load anything valid
+          // A frame that is not selected (masked out, or beyond T) has zero coefficients in LDS, but zero times what it holds
+          // is NaN if that is Inf or NaN, and the reference never touches such a frame: its lane loads the first selected
+          // frame instead, whose samples are counted anyway.  Zero times those changes no bit of a sum.  Phase 1 leaves the
+          // frame to read in LDS, so there is no select here: with one, hipcc serialised the BmH loads of the line-search passes.
+          const float2* xt = Xk + L.src[tt];
           const double2 c2 = L.c2[tt], c4 = L.c4[tt];
           float2 xf[HOS_CPW];
 #pragma unroll
@@ -245,7 +265,10 @@ __device__ void hos_pass(const hos_args& a, int k, const double* xin, bool want_
         if (n < N) {
           const double r0 = wave_sum(a2r[i]), r1 = wave_sum(a2i[i]);
           const double r2 = wave_sum(a4r[i]), r3 = wave_sum(a4i[i]);
-          if (lane == 0) { L.v2[sp][n] = make_double2(r0, r1); L.v4[sp][n] = make_double2(r2, r3); }
+          if (lane == 0) {                                 // no frame selected: every lane read frame 0, which does not count
+            L.v2[sp][n] = L.tsel ? make_double2(r0, r1) : make_double2(0.0, 0.0);
+            L.v4[sp][n] = L.tsel ? make_double2(r2, r3) : make_double2(0.0, 0.0);
+          }
         }
       }
     }

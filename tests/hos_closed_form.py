@@ -127,7 +127,17 @@ def minimize_bin(X, wuH, BmH, x0, alpha, beta, gamma, normalize, mask=None, prev
     """The optimiser of DESIGN.md 3.15 on ONE bin (X [1][N][T], ...): dict(x, f, iters, trace_f, trace_halvings, f0, g0norm,
     f_err, x_err, trace_f_err).  x_err / f_err: first-order propagation of the gradient bounds through the accepted steps, with
     the sensitivity of the gradient to x taken from the secant ||g' - g|| / ||x' - x|| of the iterates; trace_f_err[i] is f_err
-    as it stands after iteration i (the evaluation's own bound at that point plus ||g|| times the bound of the point)."""
+    as it stands after iteration i (the evaluation's own bound at that point plus ||g|| times the bound of the point).
+
+    decisions: one (iteration, kind, margin, bound) per comparison the iteration takes -- "gtol" (gnorm < gtol), "gd" (gd >= 0),
+    "armijo" (one per trial), "pr" (pr > 0), "mindelta" (df < mindelta).  margin: the distance of the compared quantity from its
+    threshold.  bound: what ONE run may be off by in that quantity, from fun_err of the evaluations involved, the drift of the
+    point (x_err, a ed for a trial point) times the slope 2 ||g|| there (dfun_hos_bf is half the derivative), and grad_err (with
+    the secant's sensitivity times the drift) through the dot products.  Two runs that both round -- the kernel and this file --
+    take the same decision when margin > 2 bound: decided says so for the whole trace, decided_ratio is the smallest
+    margin / (2 bound).  These three keys are returned with decisions=True only: the bound of an Armijo trial takes the
+    gradient at the trial point, a second evaluation per trial that the optimiser itself never makes."""
+    want_decisions = bool(options.pop("decisions", False))
     o = dict(DEFAULTS, **options)
     maxiter = int(o["maxiter"])
 
@@ -144,20 +154,33 @@ def minimize_bin(X, wuH, BmH, x0, alpha, beta, gamma, normalize, mask=None, prev
     halv = np.full(maxiter, -2, np.int32)
     step, it = 0.0, 0
     ex, ed, lip = 0.0, float(np.linalg.norm(ge)), 0.0
+    decisions = []
+    eg = float(np.linalg.norm(ge))                                     # bound of g as a vector: its own rounding, then the drift
     while it < maxiter:
         gg = float(np.dot(g, g))
         gd = float(np.dot(g, d))
         gnorm = np.sqrt(gg)
+        decisions.append((it, "gtol", abs(gnorm - o["gtol"]), eg + 4 * U * gnorm))
         if gnorm < o["gtol"]:
             break
+        e_gd = gnorm * ed + float(np.linalg.norm(d)) * eg + (len(g) + 2) * U * float(np.dot(np.abs(g), np.abs(d)))
+        decisions.append((it, "gd", abs(gd), e_gd))
         if gd >= 0:
             d, gd = -g, -gg
+            e_gd = 2 * gnorm * eg + (len(g) + 2) * U * gg
+        f_here = fe + 2 * gnorm * ex                                   # bound of f: the evaluation's own, then the drift of x
         a = 2.0 / gnorm if it == 0 else 2.0 * step
         ok = False
         for h in range(int(o["max_halvings"]) + 1):
             xt = x + a * d
             ft, fte = ev(xt, False)
-            if ft <= f + o["armijo_c1"] * a * gd:
+            rhs = f + o["armijo_c1"] * a * gd
+            if want_decisions:
+                slope = 2 * float(np.linalg.norm(ev(xt, True)[2]))     # for the bound alone: the optimiser takes no gradient here
+                e_xt = ex + a * ed + 4 * U * float(np.linalg.norm(xt))
+                decisions.append((it, "armijo", abs(ft - rhs), fte + slope * e_xt + f_here + o["armijo_c1"] * a * e_gd
+                                  + 4 * U * (abs(f) + abs(rhs))))
+            if ft <= rhs:
                 ok = True
                 break
             a *= 0.5
@@ -170,25 +193,40 @@ def minimize_bin(X, wuH, BmH, x0, alpha, beta, gamma, normalize, mask=None, prev
             lip = max(lip, float(np.linalg.norm(gn - g)) / dx)
         ex = ex + a * ed + 4 * U * float(np.linalg.norm(xt))
         pr = max(0.0, float(np.dot(gn, gn - g)) / gg)
+        egn = float(np.linalg.norm(gne)) + lip * ex
+        gnn, dgn = float(np.linalg.norm(gn)), float(np.linalg.norm(gn - g))
+        decisions.append((it, "pr", abs(float(np.dot(gn, gn - g))), egn * dgn + gnn * (egn + eg) + (len(g) + 2) * U * gnn * dgn))
         ed = float(np.linalg.norm(gne)) + lip * ex + pr * ed
         d = -gn + pr * d
         trace_f[it], halv[it] = ft, h
         trace_fe[it] = fte + float(np.sqrt(np.dot(gn, gn))) * ex
         df = abs(f - ft)
-        x, f, fe, g, step = xt, ft, fte, gn, a
+        decisions.append((it, "mindelta", abs(df - o["mindelta"]), f_here + fte + 2 * gnn * ex + 2 * U * (abs(f) + abs(ft))))
+        x, f, fe, g, step, eg = xt, ft, fte, gn, a, egn
         it += 1
         if df < o["mindelta"]:
             break
-    return dict(x=x, f=f, iters=it, trace_f=trace_f, trace_halvings=halv, f0=f0, g0norm=g0norm,
-                x_err=ex, f_err=fe + float(np.sqrt(np.dot(g, g))) * ex, trace_f_err=trace_fe)
+    out = dict(x=x, f=f, iters=it, trace_f=trace_f, trace_halvings=halv, f0=f0, g0norm=g0norm,
+               x_err=ex, f_err=fe + float(np.sqrt(np.dot(g, g))) * ex, trace_f_err=trace_fe)
+    if not want_decisions:
+        return out
+    # a margin or bound that is no number (an objective that overflowed) decides nothing
+    ratio = min([(m / (2 * b) if b > 0 else np.inf) if np.isfinite(m) and np.isfinite(b) else 0.0 for _, _, m, b in decisions],
+                default=np.inf)
+    out.update(decisions=decisions, decided=bool(ratio > 1.0), decided_ratio=float(ratio))
+    return out
 
 
 def minimize(X, wuH, BmH, x0, alpha, beta, gamma, normalize, mask=None, prev=None, **options):
-    """minimize_bin for every bin: dict of stacked arrays."""
+    """minimize_bin for every bin: dict of stacked arrays (decisions, with decisions=True: one list per bin)."""
     NS, K, dim, N = np.asarray(BmH).shape
     res = []
     for k in range(K):
         p = None if prev is None else tuple(np.asarray(q)[k:k + 1] for q in prev)
         x0k = np.zeros(2 * NS * dim) if x0 is None else x0[k]
         res.append(minimize_bin(X[k:k + 1], wuH[:, k:k + 1], BmH[:, k:k + 1], x0k, alpha, beta, gamma, normalize, mask, p, **options))
-    return {key: np.array([r[key] for r in res]) for key in res[0]}
+    out = {key: np.array([r[key] for r in res]) for key in res[0] if key != "decisions"}
+    if "decisions" in res[0]:
+        out["decisions"] = np.empty(K, object)                         # the lists differ in length
+        out["decisions"][:] = [r["decisions"] for r in res]
+    return out
