@@ -20,6 +20,32 @@ ETA = MU + G4 * (math.sqrt(2.0) + MU)
 G2 = 2 * U / (1 - 2 * U)
 
 
+# (name, (N, Lk, Bp, Q), P, S_h, rule): the plans of tests/test_gpu_conv.py's test_every_length, two per transform length the
+# other tests leave out.  "full": Q = 1 and Lk + P - 1 == N, the section exactly full.  "part": Q = 3, P = 2 Bp + r with
+# 0 < r < Bp (a short last partition) and Lk + Bp - 1 == N.  S_h: 1 = filters shared by the streams, 0 = one set per stream.
+# rule: (P, n_max) where the plan is the one btk_conv_plan picks for that call, else None.  S = 2, C = 2 everywhere; the row
+# ends inside the third tile (case_len).
+CASES = [
+    ("n1024_full", (1024, 600, 425, 1), 425, 1, None),
+    ("n1024_part", (1024, 725, 300, 3), 730, 1, None),
+    ("n2048_full", (2048, 1100, 949, 1), 949, 1, None),
+    ("n2048_part", (2048, 1349, 700, 3), 1733, 0, None),
+    ("n4096_full", (4096, 2500, 1597, 1), 1597, 1, None),
+    ("n4096_part", (4096, 2597, 1500, 3), 3700, 1, None),
+    ("n8192_full", (8192, 5000, 3193, 1), 3193, 1, None),
+    ("n8192_part", (8192, 5193, 3000, 3), 7111, 0, None),
+    ("n8192_rule_p500", (8192, 7693, 500, 1), 500, 1, (500, 16384)),
+    ("n8192_rule_p5000", (8192, 4097, 4096, 2), 5000, 1, (5000, 8192)),
+]
+CASE_S, CASE_C = 2, 2
+
+
+def case_len(plan):
+    """samples of a case's rows: two whole tiles and an odd part of the third"""
+    Lk = plan[1]
+    return 2 * Lk + Lk // 3 + 1
+
+
 def b_n(N):
     return (math.log2(N) + 1) * ETA
 

@@ -228,3 +228,32 @@ def dct_table(type, cepN, filterN):
         else:
             raise IndexError("Unknown DCT type")
     return m
+
+
+# ---------------------------------------------------------------------------------------------------------------- LDS placement
+LDS_TABLE_LIMIT = 64 * 1024
+
+
+def pcm_kernel_lds(L, vtln=None, mel=None, dct=None):
+    """(bytes of the frames' buffers, bytes of the tables) of the kernel that starts from PCM, by the size rule of its launch:
+    NF = L/2 complex points, NT = clamp(NF/4, 64, 512) threads per frame, G = 1 frame per workgroup from NT = 256, else 256/NT;
+    frames = G (8 NF + 4 (NF + 2)); tables = 8 (VTLN weights) + 4 (mel weights + cosine table) + 12 (VTLN rows + mel rows).
+    The tables are staged in LDS where frames + tables <= 64 KiB and read from global memory otherwise.  The arguments are the
+    FeTables handed to fe_process (their own counts)."""
+    NF = L // 2
+    NT = min(max(NF // 4, 64), 512)
+    G = 1 if NT >= 256 else 256 // NT
+    frames = G * (8 * NF + 4 * (NF + 2))
+    tabs = 0
+    if vtln is not None:
+        tabs += 8 * len(vtln.coef) + 12 * vtln.rows
+    if mel is not None:
+        tabs += 4 * len(mel.coef) + 12 * mel.rows
+    if dct is not None:
+        tabs += 4 * len(dct.coef)
+    return frames, tabs
+
+
+def tables_in_lds(L, vtln=None, mel=None, dct=None):
+    frames, tabs = pcm_kernel_lds(L, vtln, mel, dct)
+    return frames + tabs <= LDS_TABLE_LIMIT

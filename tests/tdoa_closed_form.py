@@ -24,20 +24,54 @@ def n_frames(nsamples, D):
     return -(-int(nsamples) // int(D))
 
 
-def windowed_frames(pcm, D):
-    """pcm [..., len] -> float32 [..., T, D]: the zero-padded frames times the window, the product rounded to float32."""
+def windowed_frames(pcm, D, window=True):
+    """pcm [..., len] -> float32 [..., T, D]: the zero-padded frames times the window, the product rounded to float32
+    (window=False: the frames as they are)."""
     pcm = np.asarray(pcm)
     n = pcm.shape[-1]
     T = n_frames(n, D)
     x = np.zeros(pcm.shape[:-1] + (T * D,), np.float64)
     x[..., :n] = pcm
-    return (x.reshape(pcm.shape[:-1] + (T, D)) * hamming(D)).astype(np.float32)
+    x = x.reshape(pcm.shape[:-1] + (T, D))
+    return (x * hamming(D) if window else x).astype(np.float32)
 
 
-def spectra(pcm, D, L):
+def spectra(pcm, D, L, window=True):
     """-> (X complex128 [..., T, L/2+1], energy float64 [..., T])"""
-    X = np.fft.rfft(windowed_frames(pcm, D).astype(np.float64), n=L, axis=-1)
+    X = np.fft.rfft(windowed_frames(pcm, D, window).astype(np.float64), n=L, axis=-1)
     return X, energy(X)
+
+
+# ---- the signal of the long-transform cases (tests/test_gpu_tdoa.py's test_long_transforms, tests/test_tdoa_cpu.py) -----------
+LONG_CASES = [(4096, 8192), (2048, 4096), (3000, 4096)]          # (D, L)
+LONG_S, LONG_C, LONG_T = 2, 3, 3
+LONG_PAIRS = [(0, 1), (0, 2), (1, 2), (2, 1)]
+LONG_THRESHOLD = 1.0e9
+LONG_DELAY = 5
+LONG_ZERO = (1, 2, 1)                                            # (stream, channel, frame) that is all zero
+LONG_QUIET = (0, 1)                                              # (stream, frame) in which channels 0 and 1 are below the threshold
+# a case whose first seed left a peak closer than 2 gcc_bound(L) to the runner-up gets another seed, never a looser condition
+LONG_SEED_SHIFT = {}
+
+
+def long_case_pcm(D, L):
+    """float32 [S][C][len], len ending inside the third frame.  Channel 0: white noise; channel 1: channel 0 delayed by
+    LONG_DELAY samples plus weaker noise; channel 2: independent noise.  Frame LONG_ZERO of one channel is all zero (a zero
+    spectrum: its pairs have no peak, and are not gated because the other channel is loud); in LONG_QUIET channels 0 and 1 are
+    scaled below LONG_THRESHOLD, so the pair (0, 1) is gated there and the pairs with channel 2 are not: the gate is an AND."""
+    S, C, T, d = LONG_S, LONG_C, LONG_T, LONG_DELAY
+    n = (T - 1) * D + D // 2 + 3
+    rng = np.random.default_rng(7000 + D + L + LONG_SEED_SHIFT.get((D, L), 0))
+    x = np.zeros((S, C, n))
+    x[:, 0] = rng.normal(size=(S, n)) * 1000.0
+    x[:, 1, d:] = x[:, 0, :n - d]
+    x[:, 1] += rng.normal(size=(S, n)) * 300.0
+    x[:, 2] = rng.normal(size=(S, n)) * 1000.0
+    s, t = LONG_QUIET
+    x[s, :2, t * D:(t + 1) * D] *= 1.0e-3
+    s, c, t = LONG_ZERO
+    x[s, c, t * D:(t + 1) * D] = 0.0
+    return x.astype(np.float32)
 
 
 def energy(X):

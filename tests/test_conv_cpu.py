@@ -91,6 +91,38 @@ def test_plan(engine, P, n_max, want):
     assert Lk + Bp - 1 <= N and Q * Bp >= P > (Q - 1) * Bp and 256 <= N <= n_max
 
 
+@pytest.mark.parametrize("case", cf.CASES, ids=[c[0] for c in cf.CASES])
+def test_listed_plans_are_consistent_and_their_tiles_cover_the_output_once(engine, case):
+    name, (N, Lk, Bp, Q), P, S_h, rule = case
+    assert Q * Bp >= P > (Q - 1) * Bp and Lk + Bp - 1 <= N and N in (1024, 2048, 4096, 8192) and S_h in (0, 1)
+    if rule is not None:
+        assert engine.conv_plan(*rule) == (N, Lk, Bp, Q) and rule[0] == P
+    elif Q == 1:
+        assert Bp == P and Lk + P - 1 == N                  # the section exactly full
+    else:
+        assert Q == 3 and 0 < P - 2 * Bp < Bp and Lk + Bp - 1 == N   # a short last partition
+    n = cf.case_len((N, Lk, Bp, Q))
+    assert 2 * Lk < n < 3 * Lk                              # the row ends inside the third tile
+    x, h = np.ones(n, np.float32), np.ones(P, np.float32)
+    for out_len in (n, n + P - 1, Lk - 1, Lk, Lk + 1):
+        tiles = cf.apply_tile_bounds(x, h, (N, Lk, Bp, Q), out_len)
+        seen = np.zeros(out_len, np.int64)
+        for first, cnt, bound in tiles:
+            assert 0 <= first and 1 <= cnt <= Lk and first + cnt <= out_len and bound > 0
+            seen[first:first + cnt] += 1
+        assert np.all(seen == 1)
+
+
+def test_every_transform_length_has_its_two_listed_plans():
+    by_n = {}
+    for name, plan, P, S_h, rule in cf.CASES:
+        if rule is None:
+            by_n.setdefault(plan[0], []).append(plan[3])
+    assert by_n == {1024: [1, 3], 2048: [1, 3], 4096: [1, 3], 8192: [1, 3]}
+    assert any(c[3] == 0 for c in cf.CASES)                 # per-stream filters somewhere
+    assert len(set(c[0] for c in cf.CASES)) == len(cf.CASES)
+
+
 def test_plan_refusals(engine):
     from distant_speech_recognition_amd import _lib
     for P, n_max in ((0, 16384), (-3, 16384), (10, 100), (10, 384), (10, 32768), (10, 128)):

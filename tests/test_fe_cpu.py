@@ -117,6 +117,42 @@ def test_dct_table_type1_is_scipy_dct2_and_unknown_type_refused(engine):
     assert e.value.code == _lib.BTK_ERR_PARAMETER
 
 
+@pytest.mark.parametrize("shape", [(800, 320, 2048), (2048, 1000, 4096), (4096, 4096, 8192)])
+def test_long_shapes_table_placement_and_left_out_count(engine, shape):
+    """The shapes tests/test_gpu_fe.py adds for the long transforms, by the host tables and the closed form alone: on which side
+    of the 64 KiB rule the kernel's tables fall (LDS at L = 2048, global memory at 4096 and 8192), and that the end-to-end LOG
+    check leaves out no more elements than its 1 % cap admits whatever the device computes (the set depends on float64 values
+    only)."""
+    from tests import test_gpu_fe as g
+    D, shift, L = shape
+    assert shape in g.SHAPES
+    powN = L // 2 + 1
+    vtln, mel, dct = g.tables(powN, 2)
+    frames, tabs = cf.pcm_kernel_lds(L, vtln, mel, dct)
+    assert frames == {2048: 12296, 4096: 24584, 8192: 49160}[L]            # 12, 24 and 48 KiB and a pad
+    assert len(dct.coef) == 13 * 30 and mel.rows == 30 and vtln.rows == powN
+    vt = cf.pcm_kernel_lds(L, vtln)[1]                                      # the VTLN table alone: about 36, 72 and 144 KiB
+    assert {2048: 36, 4096: 72, 8192: 144}[L] * 1024 <= vt <= {2048: 37, 4096: 73, 8192: 145}[L] * 1024 and vt < tabs, (vt, tabs)
+    assert cf.tables_in_lds(L, vtln, mel, dct) == g.TABLES_IN_LDS[L] == (L == 2048)
+    assert frames + tabs <= cf.LDS_TABLE_LIMIT if L == 2048 else frames + vt > cf.LDS_TABLE_LIMIT   # the VTLN table alone decides
+    assert cf.tables_in_lds(L, None, mel, dct) == (L <= 4096)              # without it the mel and cosine tables fit up to 4096
+    x, n = g.signal(D, shift)
+    assert engine.fe_frames(n, D, shift) == g.T
+    X64 = cf.spectrum64(g.closed_frames(x, n, D, shift), L)
+    P64 = cf.power64(X64, powN)
+    den = P64.sum(axis=-1)
+    off, cnt, rows = cf.mel_table(powN, 16000, 100, 6800, 30, 2)
+    M = vtln.matrix()
+    cW = float(np.abs(M).sum(axis=0).max()) * mel.abs_column_sum()
+    v64 = cf.mel_apply(P64 @ M.T, off, cnt, rows)
+    ok = v64 + 1.0 - cW * g.power_bound(L) * den[..., None] > 0
+    left = int((~ok).sum())
+    print("D=%d shift=%d L=%d: frames %d B, tables %d B, LOG end to end leaves out %d of %d" % (D, shift, L, frames, tabs, left, ok.size))
+    assert ok.size == 3960 and left <= 0.01 * ok.size
+    assert not ok[1, 0, 6].all() and ok[0].all() and ok[1, 1].all()        # the tone frame's far bands, and nothing else
+    assert left == {2048: 26, 4096: 27, 8192: 28}[L]
+
+
 @pytest.mark.parametrize("pad", [True, False])
 def test_fe_frames_is_sample_features_count(engine, pad):
     from distant_speech_recognition_amd.btk20 import feature

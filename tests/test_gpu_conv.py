@@ -158,6 +158,70 @@ def test_largest_transform_n16384(dev):
     assert _eng().conv_plan(P) == plan
 
 
+@pytest.mark.parametrize("case", cf.CASES, ids=[c[0] for c in cf.CASES])
+def test_every_length(dev, case):
+    """N = 1024 ... 8192 (conv_closed_form.CASES): a section exactly full and a three-partition filter with a short last
+    partition at each, and at N = 8192, the one length compiled under a register cap, the plans the rule itself picks."""
+    name, plan, P, S_h, rule = case
+    S, Cn, n = cf.CASE_S, cf.CASE_C, cf.case_len(plan)
+    seed = 100 + [c[0] for c in cf.CASES].index(name)
+    x, h = _signal(seed, S, n), _taps(seed + 50, (S if S_h == 0 else 1, Cn, P))
+    if rule is not None:
+        assert _eng().conv_plan(*rule) == plan
+    for out_len in (n, n + P - 1):
+        y, filt = _run(dev, x, h, plan, out_len)
+        assert y.shape == (S, Cn, out_len) and tuple(filt.H.shape) == (h.shape[0], Cn, plan[3], plan[0] // 2 + 1)
+        _check_apply("%s N=%d Lk=%d Bp=%d Q=%d P=%d S_h=%d out_len=%d" % ((name,) + plan + (P, h.shape[0], out_len)), y, x, h, plan,
+                     out_len)
+    if rule is not None and rule[1] == 16384:               # the default call picks the same plan
+        import torch
+        f = _eng().conv_filter(torch.from_numpy(h).to(dev))
+        assert (f.N, f.Lk, f.Bp, f.Q) == plan and torch.equal(torch.view_as_real(f.H), torch.view_as_real(filt.H))
+
+
+@pytest.mark.parametrize("plan,P", [((256, 100, 157, 1), 157), ((512, 313, 200, 3), 523)], ids=["n256_q1", "n512_q3"])
+def test_truncated_output(dev, plan, P):
+    """out_len < len: the row is cut inside a tile, and inside the first tile (a single partial tile, out_len < Lk).  The
+    samples that are stored have the bits of the untruncated call: a tile's position and its sums are the same."""
+    Lk = plan[1]
+    S, Cn, n = 2, 2, 4 * Lk + 50
+    x, h = _signal(30 + plan[3], S, n), _taps(31 + plan[3], (1, Cn, P))
+    whole, _ = _run(dev, x, h, plan, n)
+    for out_len in (2 * Lk + 37, Lk - 41):
+        assert out_len < n and out_len % Lk != 0
+        y, _ = _run(dev, x, h, plan, out_len)
+        assert y.shape == (S, Cn, out_len)
+        _check_apply("truncated N=%d Q=%d out_len=%d < len=%d" % (plan[0], plan[3], out_len, n), y, x, h, plan, out_len)
+        full_tiles = out_len // Lk * Lk                     # the tiles in front of the cut one see the same spans
+        assert np.array_equal(y[..., :full_tiles], whole[..., :full_tiles])
+
+
+def test_out_view_of_a_wider_buffer(dev):
+    """out= as a [..., :out_len] view of a buffer with padded rows: the padding keeps its sentinel and the samples are those of
+    the contiguous call, bit for bit."""
+    import torch
+    eng = _eng()
+    plan, P = (512, 313, 200, 3), 523
+    S, Cn, n, pad = 2, 2, 2 * 313 + 150, 24
+    x, h = _signal(40, S, n), _taps(41, (1, Cn, P))
+    xd = torch.from_numpy(x).to(dev)
+    filt = eng.conv_filter(torch.from_numpy(h).to(dev), plan=plan)
+    for out_len in (n, n + P - 1, 313 - 41):
+        want = eng.fir_convolve(xd, filt, out_len=out_len)
+        wide = torch.full((S, Cn, out_len + pad), -7.0, dtype=torch.float32, device=dev)
+        got = eng.fir_convolve(xd, filt, out_len=out_len, out=wide[..., :out_len])
+        assert got.data_ptr() == wide.data_ptr() and tuple(got.shape) == (S, Cn, out_len)
+        assert bool((wide[..., out_len:] == -7.0).all())
+        assert torch.equal(wide[..., :out_len], want)
+    _check_apply("out= view, out_len=%d" % out_len, wide[..., :out_len].cpu().numpy(), x, h, plan, out_len)
+    # a view whose rows are not contiguous is refused and nothing is written
+    wide = torch.full((S, Cn, 2 * n), -7.0, dtype=torch.float32, device=dev)
+    from distant_speech_recognition_amd import _lib
+    with pytest.raises((ValueError, _lib.BtkError)):
+        eng.fir_convolve(xd, filt, out=wide[..., ::2])
+    assert bool((wide == -7.0).all())
+
+
 def test_default_plan_and_unit_tap(dev):
     import torch
     eng = _eng()
@@ -205,6 +269,39 @@ def test_block_form(dev, step):
     assert worst <= 1.0
     # every block stands alone: block t of the row is block 0 of the row cut there
     t = 3
+    one = eng.conv_blocks(torch.from_numpy(x[:, t * step:t * step + L].copy()).to(dev), filt, L, step).cpu().numpy()
+    assert one.shape[2] == 1 and np.array_equal(one[:, :, 0], y[:, :, t])
+
+
+@pytest.mark.parametrize("L,P,step,T", [(1024, 17, 700, 3),     # another length, overlapping blocks
+                                         (8192, 17, 8192, 2),    # the length under the register cap, blocks back to back
+                                         (256, 1, 100, 4),       # P = 1: o = 1, n_out = L - 1
+                                         (256, 255, 256, 3),     # P = L - 1: one output per block
+                                         (256, 17, 300, 4)])     # a step above L: the samples between blocks are read by nobody
+def test_block_form_parameters(dev, L, P, step, T):
+    import torch
+    eng = _eng()
+    S, Cn = 2, 2
+    n = (T - 1) * step + L + min(step, L) // 2              # T blocks fit, a rest behind the last one belongs to no block
+    x, h = _signal(20 + P + step, S, n), _taps(21 + L, (1, Cn, P))
+    if step > L:                                            # what lies between the blocks must not matter: NaN there
+        for t in range(T):
+            x[:, t * step + L:(t + 1) * step] = np.nan
+    filt = eng.conv_filter(torch.from_numpy(h).to(dev), plan=(L, L - P + 1, P, 1))
+    y = eng.conv_blocks(torch.from_numpy(x).to(dev), filt, L, step).cpu().numpy()
+    assert (n - L) // step + 1 == T and y.shape == (S, Cn, T, L - P) and np.all(np.isfinite(y))
+    xz = np.nan_to_num(x, nan=0.0)                          # the closed form reads only inside the blocks; its norms want numbers
+    worst = 0.0
+    for s in range(S):
+        for c in range(Cn):
+            ref, bounds = cf.blocks_direct(xz[s], h[0, c], L, step), cf.blocks_tile_bounds(xz[s], h[0, c], L, step)
+            assert ref.shape == (T, L - P) and len(bounds) == T
+            for t in range(T):
+                worst = max(worst, float(np.sqrt(np.sum((y[s, c, t] - ref[t]) ** 2))) / bounds[t])
+    print("block form L=%d P=%d step=%d T=%d: largest block error / bound = %.2e" % (L, P, step, T, worst))
+    assert worst <= 1.0
+    # every block stands alone: block t of the row is block 0 of the row cut there
+    t = T - 1
     one = eng.conv_blocks(torch.from_numpy(x[:, t * step:t * step + L].copy()).to(dev), filt, L, step).cpu().numpy()
     assert one.shape[2] == 1 and np.array_equal(one[:, :, 0], y[:, :, t])
 

@@ -10,7 +10,8 @@ Bounds, with u = 2^-24 and B = spectra_bound(L) = (log2 L + 1) eta of tests/test
   LOG end to end: |dlog_j| <= 0.4343 c_W B_P ||P64||_1 / (v64_j + a - c_W B_P ||P64||_1) + 2u |log_j| + 2u with c_W the largest
             absolute column sum of the applied tables (their product where two are applied); elements whose denominator is not
             positive are left out and counted under the same cap.
-The kernel carries 4 frames per workgroup at L = 256 and 512 and 2 at L = 1024; T = 33 is one more than a multiple of each.
+The kernel carries 4 frames per workgroup at L = 256 and 512, 2 at L = 1024 and 1 from L = 2048; T = 33 is one more than a
+multiple of each.
 The tone frame's mel bands far from the tone lie below the end-to-end bound's own perturbation term and are the ones left
 out there: at most 30 of S C T 30 elements, which is what sets T."""
 import math
@@ -24,7 +25,13 @@ from tests.test_gpu_tdoa import spectra_bound
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-SHAPES = [(160, 160, 256), (400, 160, 512), (256, 256, 256), (256, 100, 1024)]
+SHAPES = [(160, 160, 256), (400, 160, 512), (256, 256, 256), (256, 100, 1024), (800, 320, 2048), (2048, 1000, 4096),
+          (4096, 4096, 8192)]
+# where the kernel that starts from PCM keeps the VTLN, mel and cosine tables of tables(): staged in LDS behind the frames'
+# buffers while both fit 64 KiB (fe_closed_form.pcm_kernel_lds restates the rule), read from global memory otherwise.  At
+# L = 2048 the frames take 12 KiB and the tables 44 KiB (VTLN alone 36): LDS; at 4096 and 8192 24 + 87 KiB (VTLN 72) and
+# 48 + 172 KiB (VTLN 144): global memory, the VTLN table's first numeric test there (tests/test_fe_cpu.py checks the sizes).
+TABLES_IN_LDS = {256: True, 512: True, 1024: True, 2048: True, 4096: False, 8192: False, 16384: False}
 S, C, T = 2, 2, 33
 PAD = 24                      # pcm_stride - len
 MU = 0.95
@@ -119,6 +126,7 @@ def test_every_stage(dev, shape):
     x, n = signal(D, shift)
     vtln, mel, dct = tables(powN, 1 if L == 512 else 2)
     assert eng.fe_frames(n, D, shift) == T
+    assert cf.tables_in_lds(L, vtln, mel, dct) == TABLES_IN_LDS[L], cf.pcm_kernel_lds(L, vtln, mel, dct)
     o = eng.fe_process(upload(dev, x, n), "pcm", ALL, D=D, shift=shift, L=L, vtln=vtln, mel=mel, dct=dct)
     o = {k: v.cpu().numpy() for k, v in o.items()}
     for k, d in (("spectrum", powN), ("power", powN), ("vtln", powN), ("mel", 30), ("log", 30), ("cep", 13)):
@@ -158,7 +166,8 @@ def test_every_stage(dev, shape):
     assert (~ok).sum() <= 0.01 * ok.size and np.all((err <= bound) | ~ok), r
 
 
-@pytest.mark.parametrize("shape", [(160, 160, 256), (256, 256, 256), (400, 400, 512), (256, 256, 1024)])
+@pytest.mark.parametrize("shape", [(160, 160, 256), (256, 256, 256), (400, 400, 512), (256, 256, 1024), (800, 800, 2048),
+                                   (2048, 2048, 4096), (4096, 4096, 8192)])
 def test_spectra_have_the_bits_of_tdoa_spectra(dev, shape):
     import torch
     eng = _eng()
@@ -195,7 +204,7 @@ def test_log_power_and_its_branches(dev):
             assert np.all(lg[:, :, 3] == np.float32(10.0 * math.log10(1.0e-5)))
 
 
-@pytest.mark.parametrize("shape", [(160, 160, 256), (400, 160, 512), (256, 100, 1024)])
+@pytest.mark.parametrize("shape", [(160, 160, 256), (400, 160, 512), (256, 100, 1024), (2048, 1000, 4096)])
 def test_preemphasis(dev, shape):
     import torch
     eng = _eng()
@@ -366,7 +375,7 @@ def test_device_hand_over_from_the_synthesis_bank(dev, proto256):
 def test_longest_transform_and_long_vectors_at_stage_entry(dev):
     """L = 16384: one frame per workgroup, tables read from global memory; entering at SPECTRUM with powN = L the vectors
     take one frame per workgroup in the stage kernel too.  Spectra with the bits of btk_tdoa_spectra, the rest bit-equal
-    between the two kernels."""
+    between the two kernels and, stage by stage on the GPU's own previous stage, within the bounds of the closed form."""
     import torch
     from distant_speech_recognition_amd import _lib
     eng = _eng()
@@ -389,3 +398,38 @@ def test_longest_transform_and_long_vectors_at_stage_entry(dev):
     with pytest.raises(_lib.BtkError) as e:                          # nsamples beyond the rows
         eng.fe_process(xd, "pcm", "power", D=D, L=L, nsamples=x.shape[2] + 1)
     assert e.value.code == _lib.BTK_ERR_DIMENSION
+    # the later stages against the closed form, each on the GPU's own previous stage, as in test_every_stage; with the VTLN
+    # table too, which like the others is read from global memory at this length
+    powN = L // 2 + 1
+    vtln = eng.fe_vtln_table(powN, 0.94, 0.8, 2)
+    assert not cf.tables_in_lds(L, None, mel, dct) and not cf.tables_in_lds(L, vtln, mel, dct) and not TABLES_IN_LDS[L]
+    off, cnt, rows = cf.mel_table(powN, 16000, 100, 6800, 30, 2)
+    Dm = cf.dct_table(1, 13, 30).astype(np.float64)
+    P = o["power"].cpu().numpy()
+    check_rows(o["mel"].cpu().numpy(), cf.mel_apply(P, off, cnt, rows), cf.mel_abs(P, off, cnt, rows), "L=16384 mel on power")
+    a = eng.fe_process(xd, "pcm", ALL, D=D, L=L, vtln=vtln, mel=mel, dct=dct)
+    assert torch.equal(torch.view_as_real(a["spectrum"]), torch.view_as_real(o["spectrum"])) and torch.equal(a["power"], o["power"])
+    late = eng.fe_process(a["spectrum"], "spectrum", ALL[1:], vtln=vtln, mel=mel, dct=dct)
+    for k in ALL[1:]:
+        assert torch.equal(late[k], a[k]), k
+    a = {k: v.cpu().numpy() for k, v in a.items()}
+    for k, d in (("vtln", powN), ("mel", 30), ("log", 30), ("cep", 13)):
+        assert a[k].shape == (1, 2, 3, d), (k, a[k].shape)
+    P64 = P.astype(np.float64)
+    Vw = cf.vtln_ff(P64.reshape(-1, powN).T, powN, 0.94, 0.8).T.reshape(P64.shape)
+    check_rows(a["vtln"], Vw, table_abs_apply(vtln, P64), "L=16384 vtln")
+    check_rows(a["mel"], cf.mel_apply(a["vtln"], off, cnt, rows), cf.mel_abs(a["vtln"], off, cnt, rows), "L=16384 mel")
+    check_log(a["log"], a["mel"], 1.0, 1.0, False, "L=16384 log")
+    lg = a["log"].astype(np.float64)
+    check_rows(a["cep"], lg @ Dm.T, np.abs(lg) @ np.abs(Dm).T, "L=16384 cep")
+
+
+def table_abs_apply(tab, v):
+    """sum |w| |in| per output row of an FeTable, row by row: np.abs(v) @ np.abs(tab.matrix()).T without the dense matrix"""
+    v = np.abs(np.asarray(v, np.float64))
+    w = np.abs(np.asarray(tab.coef, np.float64))
+    out = np.zeros(v.shape[:-1] + (tab.rows,))
+    for j in range(tab.rows):
+        o_, c_, s_ = int(tab.offset[j]), int(tab.count[j]), int(tab.start[j])
+        out[..., j] = v[..., o_:o_ + c_] @ w[s_:s_ + c_]
+    return out

@@ -60,16 +60,16 @@ def _eng():
     return engine
 
 
-def check_spectra(dev, pcm, D, L):
+def check_spectra(dev, pcm, D, L, window=True):
     """pcm float32 [S][C][len]: stage 1 against the closed form.  Returns the device tensors (X, energy)."""
     import torch
     eng = _eng()
     S, C, n = pcm.shape
     T = cf.n_frames(n, D)
-    Xd, ed = eng.tdoa_spectra(torch.from_numpy(pcm).to(dev), D, L)
+    Xd, ed = eng.tdoa_spectra(torch.from_numpy(pcm).to(dev), D, L, window=window)
     assert tuple(Xd.shape) == (S, C, T, L // 2 + 1) and tuple(ed.shape) == (S, C, T) and eng.tdoa_frames(n, D) == T
     X, e = Xd.cpu().numpy().astype(np.complex128), ed.cpu().numpy().astype(np.float64)
-    X64, e64 = cf.spectra(pcm, D, L)
+    X64, e64 = cf.spectra(pcm, D, L, window)
     num = np.sqrt(np.sum(np.abs(X - X64) ** 2, axis=-1))
     den = np.sqrt(np.sum(np.abs(X64) ** 2, axis=-1))
     rs = float(np.max(num / np.where(den > 0, den, 1.0)) / spectra_bound(L))
@@ -155,6 +155,43 @@ def test_full_window(dev):
     pcm = (rng.normal(size=(1, 2, 8 * 512)) * 1000).astype(np.float32)
     Xd, ed = check_spectra(dev, pcm, 512, 512)
     check_gcc(dev, Xd, ed, [(0, 1)], 64.0, 512, "full window")
+
+
+@pytest.mark.parametrize("D,L", cf.LONG_CASES, ids=["D%d-L%d" % c for c in cf.LONG_CASES])
+def test_long_transforms(dev, D, L):
+    """L = 4096 and 8192, which the Kinect cases leave out: both stages against float64 on tdoa_closed_form.long_case_pcm (two
+    streams, three channels, a delayed copy, a zero frame, a gated frame).  No frame may be left out of the lag comparison at 24
+    work units; tests/test_tdoa_cpu.py shows that the closed form's own margins admit that."""
+    pcm = cf.long_case_pcm(D, L)
+    S, C, T = cf.LONG_S, cf.LONG_C, cf.LONG_T
+    assert pcm.shape[:2] == (S, C) and cf.n_frames(pcm.shape[-1], D) == T and pcm.shape[-1] % D != 0
+    Xd, ed = check_spectra(dev, pcm, D, L)
+    e64 = cf.spectra(pcm, D, L)[1]
+    lag, h, refs = check_gcc(dev, Xd, ed, cf.LONG_PAIRS, cf.LONG_THRESHOLD, L, "long D=%d L=%d" % (D, L), e64=e64)
+    # the frames without a peak are the ones the signal was built to have, and no others
+    gated = np.zeros((S, len(cf.LONG_PAIRS), T), bool)
+    zero = np.zeros_like(gated)
+    gated[cf.LONG_QUIET[0], cf.LONG_PAIRS.index((0, 1)), cf.LONG_QUIET[1]] = True
+    for p, pair in enumerate(cf.LONG_PAIRS):
+        zero[cf.LONG_ZERO[0], p, cf.LONG_ZERO[2]] = cf.LONG_ZERO[1] in pair
+    assert np.array_equal(np.stack([r[3] for r in refs]), gated) and np.array_equal(np.stack([r[4] for r in refs]), zero)
+    assert np.array_equal(lag == cf.NO_PEAK, gated | zero)
+    # the delayed copy: channel 1 lags channel 0 wherever both are loud
+    p01 = cf.LONG_PAIRS.index((0, 1))
+    loud = ~(gated | zero)[:, p01]
+    assert np.all(lag[:, p01][loud] == -cf.LONG_DELAY)
+    # (2, 1) mirrors (1, 2)
+    a, b = lag[:, cf.LONG_PAIRS.index((1, 2))], lag[:, cf.LONG_PAIRS.index((2, 1))]
+    ok = a != cf.NO_PEAK
+    assert np.array_equal(b[ok], np.where((a[ok] == 0) | (a[ok] == -L // 2), a[ok], -a[ok]))
+
+
+def test_no_window_full_frame_l8192(dev):
+    """window=False with D = L = 8192: the transform with nothing in front of it."""
+    rng = np.random.default_rng(12)
+    L = 8192
+    pcm = (rng.normal(size=(2, 2, 2 * L + 777)) * 1000).astype(np.float32)
+    check_spectra(dev, pcm, L, L, window=False)
 
 
 def test_all_pairs_64_channels(dev):

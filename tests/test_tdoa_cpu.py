@@ -80,6 +80,41 @@ def test_closed_form_gate_and_zero_bin():
     assert cf.peak(np.array([0.0, 0.1, -0.7, 0.2]))[0] == -2
 
 
+@pytest.mark.parametrize("D,L", cf.LONG_CASES, ids=["D%d-L%d" % c for c in cf.LONG_CASES])
+def test_long_case_signal_leaves_no_frame_out(D, L):
+    """The signal of tests/test_gpu_tdoa.py's test_long_transforms, by the closed form alone: exactly the built-in frames are
+    gated or zero, every other peak is more than 2 gcc_bound(L) ahead of the runner-up (so the GPU test, whose 1 % cap admits
+    no left-out frame at 24 work units, can hold every lag to the closed form's), and the delayed copy is found."""
+    from tests.test_gpu_tdoa import gcc_bound, energy_bound
+    pcm = cf.long_case_pcm(D, L)
+    S, C, T, pairs = cf.LONG_S, cf.LONG_C, cf.LONG_T, cf.LONG_PAIRS
+    assert pcm.shape == (S, C, (T - 1) * D + D // 2 + 3) and pcm.dtype == np.float32 and cf.n_frames(pcm.shape[-1], D) == T
+    assert 0.01 * S * len(pairs) * T < 1                     # the cap of check_gcc admits no left-out frame
+    X, e = rounded_spectra(pcm, D, L)
+    # every energy is clear of the threshold by far more than the kernel's energy bound
+    assert np.all(np.abs(e - cf.LONG_THRESHOLD) > 100 * energy_bound(L) * e)
+    smallest = np.inf
+    for s in range(S):
+        lag, height, margin, gated, zero = cf.gcc_peaks(X[s], e[s], pairs, cf.LONG_THRESHOLD)
+        for p, pair in enumerate(pairs):
+            for t in range(T):
+                assert gated[p, t] == ((s, t) == cf.LONG_QUIET and pair == (0, 1)), (s, p, t)
+                assert zero[p, t] == ((s, t) == (cf.LONG_ZERO[0], cf.LONG_ZERO[2]) and cf.LONG_ZERO[1] in pair), (s, p, t)
+        ok = ~(gated | zero)
+        smallest = min(smallest, float(margin[ok].min()))
+        assert np.all(margin[ok] > 2 * gcc_bound(L)), (s, float(margin[ok].min()), 2 * gcc_bound(L))
+        assert np.all(lag[0][ok[0]] == -cf.LONG_DELAY)
+    print("long case D=%d L=%d: smallest margin %.3g against 2B = %.3g" % (D, L, smallest, 2 * gcc_bound(L)))
+
+
+def test_closed_form_without_window():
+    x = np.arange(1, 11, dtype=np.float32)
+    f = cf.windowed_frames(x, 4, window=False)
+    assert f.dtype == np.float32 and np.array_equal(f, [[1, 2, 3, 4], [5, 6, 7, 8], [9, 10, 0, 0]])
+    X, e = cf.spectra(x, 4, 8, window=False)
+    assert np.allclose(X, np.fft.rfft(f.astype(np.float64), n=8, axis=-1)) and X[0, 0] == 10
+
+
 def test_closed_form_window_and_frames():
     x = np.arange(1, 11, dtype=np.float32)
     f = cf.windowed_frames(x, 4)
