@@ -4,32 +4,26 @@
 // matrix/gslmatrix.cc:107-131), for every frame of a block in one launch.
 //
 // fe_pcm_kernel: G frames per workgroup, each on NT threads.  A frame is loaded (overlapping frames read the same samples from
-// L2), pre-emphasised, windowed and transformed in LDS exactly as tdoa_spectra_kernel does it (fft_long.h, the same split
-// step: with the Hamming window, no pre-emphasis and shift = D the spectra have that kernel's bits).  The power vector stays in
+// L2), pre-emphasised, windowed and transformed in LDS as tdoa_spectra_kernel does it (fft_long.h, rfft_long.h's split step:
+// with the Hamming window, no pre-emphasis and shift = D the spectra have that kernel's bits).  The power vector stays in
 // LDS; the later stages ping-pong between it and the transform's buffer, which is free by then, and only the requested stages
 // are written to HBM.  The tables (a few KB at ASR sizes: the mel rows are 2-16 coefficients long and stored by row) are staged
 // into LDS while they fit beside the frames, and read through L2 otherwise.
 // fe_stage_kernel: the same device functions for vectors that enter at SPECTRUM or later.
 // VTLN, MEL and CEP accumulate each output in float64 in the order of their row and round once, so a stage gives the same bits
 // whichever kernel runs it and however the frames are grouped.
-#include <atomic>
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <utility>
 #include <vector>
 #include "btk_internal.h"
-#include "fft_long.h"
+#include "rfft_long.h"
 
 namespace {
 
-constexpr int FE_MIN_L = 256, FE_MAX_L = 16384;
 constexpr size_t FE_LDS_TABLE_LIMIT = 64 * 1024;   // tables go to LDS while the workgroup stays within this
 constexpr size_t FE_LDS_MAX = 160 * 1024;
 
 template <int LOG2NF> struct fe_cfg {
-  static constexpr int NF = 1 << LOG2NF;
-  static constexpr int NT = NF / 4 < 64 ? 64 : (NF / 4 > 512 ? 512 : NF / 4);   // threads per frame, as tdoa_cfg
+  static constexpr int NT = rfft_threads<LOG2NF>;                                // threads per frame
   static constexpr int G = NT >= 256 ? 1 : 256 / NT;                             // frames per workgroup: 256 threads at least
 };
 constexpr int FE_STAGE_NT = 64, FE_STAGE_G = 4;
@@ -168,7 +162,6 @@ template <int LOG2NF, int NT, int G>
 __global__ __launch_bounds__(NT* G) void fe_pcm_kernel(const float* __restrict__ pcm, fe_dev p)
 {
   constexpr int NF = 1 << LOG2NF, L = 2 * NF;
-  constexpr int TS = BTK_LONGFFT_TWN / (2 * NF);   // table entries per step of exp(-i 2 pi / L)
   constexpr int PWS = (NF + 2) & ~1;               // floats per frame of the power vector (even: the tables behind are 8-byte aligned)
   extern __shared__ float2 smem[];
   const int tid = threadIdx.x, g = tid / NT, lt = tid % NT;
@@ -204,14 +197,10 @@ __global__ __launch_bounds__(NT* G) void fe_pcm_kernel(const float* __restrict__
   }
   __syncthreads();
   fft_long<LOG2NF, NT, -1>(buf, p.tw, lt);
-  // split step of tdoa_spectra_kernel: X[k] = E[k] + w^k O[k], X[NF-k] = conj(E[k] - w^k O[k]), w = exp(-i 2 pi / L)
   float2* Xr = valid && p.oX ? p.oX + f * (NF + 1) : nullptr;
   for (int k = lt; k <= NF / 2; k += NT) {
-    const float2 A = buf[k], B = cconjf(buf[(NF - k) & (NF - 1)]);
-    const float2 E = make_float2(0.5f * (A.x + B.x), 0.5f * (A.y + B.y));
-    const float2 O = make_float2(0.5f * (A.y - B.y), -0.5f * (A.x - B.x));   // (A - B) / (2 i)
-    const float2 wO = k == 0 ? O : cmulf(O, p.tw[k * TS]);
-    const float2 x0 = caddf(E, wO), x1 = cconjf(csubf(E, wO));
+    float2 x0, x1;
+    rfft_split<NF>(buf, p.tw, k, NF - k, x0, x1);
     if (Xr) Xr[k] = x0;
     pw[k] = fe_abs2(x0);
     if (k != NF - k) {
@@ -258,71 +247,6 @@ __global__ __launch_bounds__(FE_STAGE_NT* G) void fe_stage_kernel(const void* __
   fe_tail(p, tb, a, b, n, 0, false, valid ? f : -1, lt, NT);
 }
 
-// ---- tables: one twiddle table per device, one window per (device, D); built in float64 on the host, uploaded once (the
-// rules of tdoa_kernels.hip: nothing is ever freed, the distinct window lengths of a process are bounded by bytes)
-std::mutex g_mu;
-std::map<int, float2*> g_tw;
-std::map<std::pair<int, int>, double*> g_win;
-constexpr size_t FE_WINDOW_BYTES_MAX = 64 * sizeof(double) * FE_MAX_L;
-size_t g_win_bytes = 0;
-
-int fe_twiddles(const float2** out)
-{
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_tw.find(dev);
-  if (it == g_tw.end()) {
-    std::vector<float2> h(BTK_LONGFFT_TWN);
-    for (int j = 0; j < BTK_LONGFFT_TWN; j++) {
-      const double a = -2.0 * M_PI * (double)j / (double)BTK_LONGFFT_TWN;
-      h[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    float2* d = nullptr;
-    BTK_HIP_CHECK(hipMalloc(&d, sizeof(float2) * BTK_LONGFFT_TWN));
-    BTK_HIP_CHECK(hipMemcpy(d, h.data(), sizeof(float2) * BTK_LONGFFT_TWN, hipMemcpyHostToDevice));
-    it = g_tw.emplace(dev, d).first;
-  }
-  *out = it->second;
-  return BTK_OK;
-}
-
-int fe_window(int D, const double** out)
-{
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_win.find({dev, D});
-  if (it == g_win.end()) {
-    if (g_win_bytes + sizeof(double) * D > FE_WINDOW_BYTES_MAX)
-      return btk_set_error(BTK_ERR_ALLOCATION, "btk_fe_process: more than %zu bytes of distinct window lengths in one process",
-                           FE_WINDOW_BYTES_MAX);
-    std::vector<double> h(D);                      // HammingFeature's window, in its own order of operations (feature.cc:1181-1183)
-    const double temp = 2. * M_PI / (double)(D - 1);
-    for (int i = 0; i < D; i++) h[i] = 0.54 - 0.46 * std::cos(temp * i);
-    double* d = nullptr;
-    BTK_HIP_CHECK(hipMalloc(&d, sizeof(double) * D));
-    BTK_HIP_CHECK(hipMemcpy(d, h.data(), sizeof(double) * D, hipMemcpyHostToDevice));
-    g_win_bytes += sizeof(double) * D;
-    it = g_win.emplace(std::make_pair(dev, D), d).first;
-  }
-  *out = it->second;
-  return BTK_OK;
-}
-
-// a workgroup may declare more LDS than the default limit: raised once per kernel instantiation and device
-template <int TAG, class K> int fe_allow_lds(K kern)
-{
-  static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (done.load(std::memory_order_acquire) & bit) return BTK_OK;
-  BTK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FE_LDS_MAX));
-  done.fetch_or(bit, std::memory_order_release);
-  return BTK_OK;
-}
-
 size_t fe_table_bytes(const fe_dev& p)
 {
   return sizeof(double) * p.n_vw + sizeof(float) * ((size_t)p.n_mw + p.n_dct) +
@@ -332,12 +256,12 @@ size_t fe_table_bytes(const fe_dev& p)
 template <int LOG2NF> int launch_pcm(const float* pcm, fe_dev p, hipStream_t st)
 {
   constexpr int NF = 1 << LOG2NF, NT = fe_cfg<LOG2NF>::NT, G = fe_cfg<LOG2NF>::G, PWS = (NF + 2) & ~1;
-  auto kern = fe_pcm_kernel<LOG2NF, NT, G>;
+  constexpr auto kern = fe_pcm_kernel<LOG2NF, NT, G>;
   size_t lds = sizeof(float2) * G * NF + sizeof(float) * G * PWS;
   const size_t tb = fe_table_bytes(p);
   p.tab_lds = lds + tb <= FE_LDS_TABLE_LIMIT;
   if (p.tab_lds) lds += tb;
-  if (int rc = fe_allow_lds<LOG2NF>(kern)) return rc;
+  if (int rc = btk_allow_lds<kern>(FE_LDS_MAX)) return rc;
   const long blocks = (p.nframes + G - 1) / G;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT * G), lds, st, pcm, p);
   BTK_HIP_CHECK(hipGetLastError());
@@ -350,10 +274,9 @@ template <int G> int launch_stage_g(const void* in, fe_dev p, int L, int cap, hi
   const size_t tb = fe_table_bytes(p);
   p.tab_lds = lds + tb <= FE_LDS_TABLE_LIMIT;
   if (p.tab_lds) lds += tb;
-  auto kern = fe_stage_kernel<G>;
-  if (int rc = fe_allow_lds<100 + G>(kern)) return rc;
+  if (int rc = btk_allow_lds<fe_stage_kernel<G>>(FE_LDS_MAX)) return rc;
   const long blocks = (p.nframes + G - 1) / G;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(FE_STAGE_NT * G), lds, st, in, p, L, cap);
+  hipLaunchKernelGGL(fe_stage_kernel<G>, dim3((unsigned)blocks), dim3(FE_STAGE_NT * G), lds, st, in, p, L, cap);
   BTK_HIP_CHECK(hipGetLastError());
   return BTK_OK;
 }
@@ -367,14 +290,6 @@ int launch_stage(const void* in, fe_dev p, int L, int maxdim, hipStream_t st)
   if (sizeof(float) * 2 * (size_t)cap > FE_LDS_MAX)
     return btk_set_error(BTK_ERR_DIMENSION, "btk_fe_process: stage length %d does not fit a workgroup's LDS", maxdim);
   return launch_stage_g<1>(in, p, L, cap, st);
-}
-
-int fe_log2_of_L(int L)
-{
-  if (L < FE_MIN_L || L > FE_MAX_L || (L & (L - 1))) return -1;
-  int n = 0;
-  while ((1 << n) < L) n++;
-  return n;
 }
 
 // mel_ / hertz_ of MelFeature::SparseMatrix_ (feature/feature.cc:1892-1902)
@@ -415,9 +330,9 @@ int btk_fe_process(const btk_fe_params* q, const void* in, void* stream)
   int n;                                           // length of the vector the next stage reads
   if (q->in_stage <= BTK_FE_SPECTRUM) {
     L = q->L;
-    lg = fe_log2_of_L(L);
+    lg = longfft_log2(L);
     if (lg < 0)
-      return btk_set_error(BTK_ERR_DIMENSION, "btk_fe_process: L=%d must be a power of two from %d to %d", L, FE_MIN_L, FE_MAX_L);
+      return btk_set_error(BTK_ERR_DIMENSION, "btk_fe_process: L=%d must be a power of two from %d to %d", L, RFFT_MIN_L, RFFT_MAX_L);
     if (last >= BTK_FE_POWER && q->powN != L / 2 + 1 && q->powN != L)
       return btk_set_error(BTK_ERR_DIMENSION, "btk_fe_process: number of power coefficients %d does not match FFT length %d", q->powN, L);
     p.powN = q->powN;
@@ -486,19 +401,11 @@ int btk_fe_process(const btk_fe_params* q, const void* in, void* stream)
     p.n_mw = q->mel_nw;
   }
   if (q->in_stage == BTK_FE_PCM) {
-    int rc = fe_twiddles(&p.tw);
-    if (!rc && q->window == BTK_TDOA_WINDOW_HAMMING) rc = fe_window(q->D, &p.win);
+    int rc = longfft_twiddles(&p.tw);
+    if (!rc && q->window == BTK_TDOA_WINDOW_HAMMING) rc = longfft_hamming("btk_fe_process", q->D, &p.win);
     if (rc) return rc;
     const float* pcm = reinterpret_cast<const float*>(in);
-    switch (lg - 1) {
-      case 7: return launch_pcm<7>(pcm, p, st);
-      case 8: return launch_pcm<8>(pcm, p, st);
-      case 9: return launch_pcm<9>(pcm, p, st);
-      case 10: return launch_pcm<10>(pcm, p, st);
-      case 11: return launch_pcm<11>(pcm, p, st);
-      case 12: return launch_pcm<12>(pcm, p, st);
-      default: return launch_pcm<13>(pcm, p, st);
-    }
+    return longfft_dispatch(lg, [&](auto n) { return launch_pcm<decltype(n)::value>(pcm, p, st); });
   }
   return launch_stage(in, p, L, maxdim, st);
 }

@@ -3,25 +3,12 @@
 // (PHATFeature.next / TDOAFeature.next, lib/pytdoa.py:32-54, :87-114), for every frame of a block in one launch each.
 //
 // Both kernels hold one L-point real transform per workgroup as an L/2-point complex transform in LDS (fft_long.h: twiddles
-// from a float64-rounded table read through L2, mu = 2^-24) with the usual split / pre-twist step, so at L = 16384 a workgroup
-// declares 64 KB and two of them share a CU.  The correlation never leaves LDS unless the caller asks for it.
-#include <atomic>
-#include <cmath>
-#include <map>
-#include <mutex>
-#include <utility>
-#include <vector>
+// from a float64-rounded table read through L2, mu = 2^-24) with the split / pre-twist step of rfft_long.h, so at L = 16384 a
+// workgroup declares 64 KB and two of them share a CU.  The correlation never leaves LDS unless the caller asks for it.
 #include "btk_internal.h"
-#include "fft_long.h"
+#include "rfft_long.h"
 
 namespace {
-
-constexpr int TDOA_MIN_L = 256, TDOA_MAX_L = 16384;
-
-template <int LOG2NF> struct tdoa_cfg {
-  static constexpr int NF = 1 << LOG2NF;
-  static constexpr int NT = NF / 4 < 64 ? 64 : (NF / 4 > 512 ? 512 : NF / 4);
-};
 
 // ---- stage 1: Hamming window (float64 product rounded to float32; win == NULL: the frame as it is), zero padding to L, forward
 // real transform, frame energy.  One workgroup per (stream, channel, frame); rows of pcm are pcm_stride apart.
@@ -31,7 +18,6 @@ __global__ __launch_bounds__(NT) void tdoa_spectra_kernel(const float* __restric
                                                           float2* __restrict__ X, float* __restrict__ energy)
 {
   constexpr int NF = 1 << LOG2NF;
-  constexpr int TS = BTK_LONGFFT_TWN / (2 * NF);   // table entries per step of exp(-i 2 pi / L)
   extern __shared__ float2 buf[];
   __shared__ float red[NT / 64];
   const int tid = threadIdx.x;
@@ -48,15 +34,11 @@ __global__ __launch_bounds__(NT) void tdoa_spectra_kernel(const float* __restric
   }
   __syncthreads();
   fft_long<LOG2NF, NT, -1>(buf, tw, tid);
-  // split step: Z = E + i O of the even / odd samples, X[k] = E[k] + w^k O[k], X[NF-k] = conj(E[k] - w^k O[k]), w = exp(-i 2 pi / L)
   float2* Xr = X + f * (NF + 1);
   float e = 0.f;
   for (int k = tid; k <= NF / 2; k += NT) {
-    const float2 A = buf[k], B = cconjf(buf[(NF - k) & (NF - 1)]);
-    const float2 E = make_float2(0.5f * (A.x + B.x), 0.5f * (A.y + B.y));
-    const float2 O = make_float2(0.5f * (A.y - B.y), -0.5f * (A.x - B.x));   // (A - B) / (2 i)
-    const float2 wO = k == 0 ? O : cmulf(O, tw[k * TS]);
-    const float2 x0 = caddf(E, wO), x1 = cconjf(csubf(E, wO));
+    float2 x0, x1;
+    rfft_split<NF>(buf, tw, k, NF - k, x0, x1);
     Xr[k] = x0;
     e += x0.x * x0.x + x0.y * x0.y;
     if (k != NF - k) {
@@ -99,7 +81,6 @@ __global__ __launch_bounds__(NT) void tdoa_gcc_kernel(const float2* __restrict__
                                                       float* __restrict__ height, float* __restrict__ gcc)
 {
   constexpr int NF = 1 << LOG2NF, L = 2 * NF;
-  constexpr int TS = BTK_LONGFFT_TWN / L;
   extern __shared__ float2 buf[];
   __shared__ float redv[NT / 64];
   __shared__ int redi[NT / 64];
@@ -121,18 +102,13 @@ __global__ __launch_bounds__(NT) void tdoa_gcc_kernel(const float2* __restrict__
   const float2* Xa = X + fa * (NF + 1);
   const float2* Xb = X + fb * (NF + 1);
   bool zero = false;
-  // irfft as an NF-point complex transform: Z[k] = (G[k] + conj G[NF-k]) + i v^k (G[k] - conj G[NF-k]), v = exp(+i 2 pi / L);
-  // the imaginary parts of G[0] and G[NF] are ignored, as numpy's irfft ignores them
+  // irfft as an NF-point complex transform
   for (int k = tid; k <= NF / 2; k += NT) {
     const float2 Gk = phat_unit(Xa[k], Xb[k], zero), Gm = phat_unit(Xa[NF - k], Xb[NF - k], zero);
-    if (k == 0) {
-      buf[0] = make_float2(Gk.x + Gm.x, Gk.x - Gm.x);
-    } else {
-      const float2 Sm = make_float2(Gk.x + Gm.x, Gk.y - Gm.y), Df = make_float2(Gk.x - Gm.x, Gk.y + Gm.y);
-      const float2 Q = cmulf(Df, cconjf(tw[k * TS]));
-      buf[k] = make_float2(Sm.x - Q.y, Sm.y + Q.x);
-      if (k != NF - k) buf[NF - k] = make_float2(Sm.x + Q.y, Q.x - Sm.y);
-    }
+    float2 zk, zm;
+    rfft_pretwist<NF>(Gk, Gm, tw, k, zk, zm);
+    buf[k] = zk;
+    if (k != 0 && k != NF - k) buf[NF - k] = zm;
   }
   // a zero bin makes every lag NaN in the reference (0/0), and no NaN compares greater: no peak
   if (__syncthreads_or(zero)) {
@@ -168,92 +144,14 @@ __global__ __launch_bounds__(NT) void tdoa_gcc_kernel(const float2* __restrict__
   }
 }
 
-// ---- tables: one twiddle table per device, one window per (device, D); built in float64 on the host, uploaded once
-std::mutex g_mu;
-std::map<int, float2*> g_tw;
-std::map<std::pair<int, int>, double*> g_win;
-
-int tdoa_twiddles(const float2** out)
-{
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_tw.find(dev);
-  if (it == g_tw.end()) {
-    std::vector<float2> h(BTK_LONGFFT_TWN);
-    for (int j = 0; j < BTK_LONGFFT_TWN; j++) {
-      const double a = -2.0 * M_PI * (double)j / (double)BTK_LONGFFT_TWN;
-      h[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    float2* d = nullptr;
-    BTK_HIP_CHECK(hipMalloc(&d, sizeof(float2) * BTK_LONGFFT_TWN));
-    BTK_HIP_CHECK(hipMemcpy(d, h.data(), sizeof(float2) * BTK_LONGFFT_TWN, hipMemcpyHostToDevice));
-    it = g_tw.emplace(dev, d).first;
-  }
-  *out = it->second;
-  return BTK_OK;
-}
-
-// Windows live as long as the process: a pointer handed out may belong to a launch another host thread has not made yet, so
-// nothing is ever freed.  Bounded by bytes instead (64 lengths of the largest window); a process that asks for more distinct
-// lengths than fit gets BTK_ERR_ALLOCATION.  The first use of a length (and of a device) allocates and copies, so it cannot be
-// part of a stream capture; every later launch with that length is capturable.
-constexpr size_t TDOA_WINDOW_BYTES_MAX = 64 * sizeof(double) * TDOA_MAX_L;
-size_t g_win_bytes = 0;
-
-int tdoa_window(int D, const double** out)
-{
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  auto it = g_win.find({dev, D});
-  if (it == g_win.end()) {
-    if (g_win_bytes + sizeof(double) * D > TDOA_WINDOW_BYTES_MAX)
-      return btk_set_error(BTK_ERR_ALLOCATION, "btk_tdoa_spectra: more than %zu bytes of distinct window lengths in one process",
-                           TDOA_WINDOW_BYTES_MAX);
-    std::vector<double> h(D);                      // HammingFeature's window, in its own order of operations (feature.cc:1181-1183)
-    const double temp = 2. * M_PI / (double)(D - 1);
-    for (int i = 0; i < D; i++) h[i] = 0.54 - 0.46 * std::cos(temp * i);
-    double* d = nullptr;
-    BTK_HIP_CHECK(hipMalloc(&d, sizeof(double) * D));
-    BTK_HIP_CHECK(hipMemcpy(d, h.data(), sizeof(double) * D, hipMemcpyHostToDevice));
-    g_win_bytes += sizeof(double) * D;
-    it = g_win.emplace(std::make_pair(dev, D), d).first;
-  }
-  *out = it->second;
-  return BTK_OK;
-}
-
-// a workgroup's LDS exceeds the default limit at the largest transform: raised once per kernel instantiation and device
-// (TAG tells the instantiations apart: kernels of one signature share a function-pointer type)
-template <int TAG, class K> int tdoa_allow_lds(K kern, size_t lds)
-{
-  static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  BTK_HIP_CHECK(hipGetDevice(&dev));
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (done.load(std::memory_order_acquire) & bit) return BTK_OK;
-  BTK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  done.fetch_or(bit, std::memory_order_release);
-  return BTK_OK;
-}
-
-int log2_of_L(int L)
-{
-  if (L < TDOA_MIN_L || L > TDOA_MAX_L || (L & (L - 1))) return -1;
-  int n = 0;
-  while ((1 << n) < L) n++;
-  return n;
-}
-
 template <int LOG2NF>
 int launch_spectra(const float* pcm, long len, long pcm_stride, long rows, long T, int D, const double* win, const float2* tw,
                    void* X, void* energy, hipStream_t st)
 {
-  constexpr int NF = 1 << LOG2NF, NT = tdoa_cfg<LOG2NF>::NT;
-  auto kern = tdoa_spectra_kernel<LOG2NF, NT>;
+  constexpr int NF = 1 << LOG2NF, NT = rfft_threads<LOG2NF>;
+  constexpr auto kern = tdoa_spectra_kernel<LOG2NF, NT>;
   const size_t lds = sizeof(float2) * NF;
-  if (int rc = tdoa_allow_lds<2 * LOG2NF>(kern, lds)) return rc;
+  if (int rc = btk_allow_lds<kern>(lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(rows * T)), dim3(NT), lds, st, pcm, len, pcm_stride, T, D, win, tw,
                      reinterpret_cast<float2*>(X), reinterpret_cast<float*>(energy));
   BTK_HIP_CHECK(hipGetLastError());
@@ -264,10 +162,10 @@ template <int LOG2NF>
 int launch_gcc(const void* X, const void* energy, const int* pairs, int P, float thr, int S, int C, long T, const float2* tw,
                void* lag, void* height, void* gcc, hipStream_t st)
 {
-  constexpr int NF = 1 << LOG2NF, NT = tdoa_cfg<LOG2NF>::NT;
-  auto kern = tdoa_gcc_kernel<LOG2NF, NT>;
+  constexpr int NF = 1 << LOG2NF, NT = rfft_threads<LOG2NF>;
+  constexpr auto kern = tdoa_gcc_kernel<LOG2NF, NT>;
   const size_t lds = sizeof(float2) * NF;
-  if (int rc = tdoa_allow_lds<2 * LOG2NF + 1>(kern, lds)) return rc;
+  if (int rc = btk_allow_lds<kern>(lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)((long)S * T * P)), dim3(NT), lds, st, reinterpret_cast<const float2*>(X),
                      reinterpret_cast<const float*>(energy), pairs, P, thr, C, T, tw, reinterpret_cast<int*>(lag),
                      reinterpret_cast<float*>(height), reinterpret_cast<float*>(gcc));
@@ -284,9 +182,9 @@ long btk_tdoa_frames(long len, int D) { return (len > 0 && D > 0) ? (len + D - 1
 int btk_tdoa_spectra(const float* pcm, long len, long pcm_stride, int S, int C, int D, int L, int window, void* X, void* energy,
                      void* stream)
 {
-  const int lg = log2_of_L(L);
+  const int lg = longfft_log2(L);
   if (lg < 0)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_spectra: L=%d must be a power of two from %d to %d", L, TDOA_MIN_L, TDOA_MAX_L);
+    return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_spectra: L=%d must be a power of two from %d to %d", L, RFFT_MIN_L, RFFT_MAX_L);
   if (D < 2 || D > L) return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_spectra: window length D=%d, need 2 <= D <= L=%d", D, L);
   if (S < 1 || C < 1 || len < 1 || pcm_stride < len)
     return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_spectra: S=%d C=%d len=%ld pcm_stride=%ld", S, C, len, pcm_stride);
@@ -297,45 +195,32 @@ int btk_tdoa_spectra(const float* pcm, long len, long pcm_stride, int S, int C, 
   if (rows * T > 0x7fffffffL) return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_spectra: %ld frames in one launch", rows * T);
   const float2* tw;
   const double* win = nullptr;
-  int rc = tdoa_twiddles(&tw);
-  if (!rc && window == BTK_TDOA_WINDOW_HAMMING) rc = tdoa_window(D, &win);
+  int rc = longfft_twiddles(&tw);
+  if (!rc && window == BTK_TDOA_WINDOW_HAMMING) rc = longfft_hamming("btk_tdoa_spectra", D, &win);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  switch (lg - 1) {
-    case 7: return launch_spectra<7>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    case 8: return launch_spectra<8>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    case 9: return launch_spectra<9>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    case 10: return launch_spectra<10>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    case 11: return launch_spectra<11>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    case 12: return launch_spectra<12>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-    default: return launch_spectra<13>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
-  }
+  return longfft_dispatch(lg, [&](auto n) {
+    return launch_spectra<decltype(n)::value>(pcm, len, pcm_stride, rows, T, D, win, tw, X, energy, st);
+  });
 }
 
 int btk_tdoa_gcc_peaks(const void* X, const void* energy, const int* pairs, int P, float energy_threshold, int S, int C, long T,
                        int L, void* lag, void* height, void* gcc, void* stream)
 {
-  const int lg = log2_of_L(L);
+  const int lg = longfft_log2(L);
   if (lg < 0)
-    return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_gcc_peaks: L=%d must be a power of two from %d to %d", L, TDOA_MIN_L, TDOA_MAX_L);
+    return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_gcc_peaks: L=%d must be a power of two from %d to %d", L, RFFT_MIN_L, RFFT_MAX_L);
   if (S < 1 || C < 1 || T < 1 || P < 1)
     return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_gcc_peaks: S=%d C=%d T=%ld P=%d", S, C, T, P);
   if (!X || !energy || !pairs || !lag || !height) return btk_set_error(BTK_ERR_PARAMETER, "btk_tdoa_gcc_peaks: null argument");
   if ((long)S * T * P > 0x7fffffffL)
     return btk_set_error(BTK_ERR_DIMENSION, "btk_tdoa_gcc_peaks: %ld correlations in one launch", (long)S * T * P);
   const float2* tw;
-  int rc = tdoa_twiddles(&tw);
-  if (rc) return rc;
+  if (int rc = longfft_twiddles(&tw)) return rc;
   hipStream_t st = as_stream(stream);
-  switch (lg - 1) {
-    case 7: return launch_gcc<7>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    case 8: return launch_gcc<8>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    case 9: return launch_gcc<9>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    case 10: return launch_gcc<10>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    case 11: return launch_gcc<11>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    case 12: return launch_gcc<12>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-    default: return launch_gcc<13>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
-  }
+  return longfft_dispatch(lg, [&](auto n) {
+    return launch_gcc<decltype(n)::value>(X, energy, pairs, P, energy_threshold, S, C, T, tw, lag, height, gcc, st);
+  });
 }
 
 }  // extern "C"
