@@ -21,7 +21,6 @@
 
 class AcousticEchoCancellationNode_ : public VectorComplexFeatureStream, public BlockSource {
  public:
-  virtual ~AcousticEchoCancellationNode_();
   virtual const gsl_vector_complex* next(int frame_no = -5);
   virtual void reset();
   // frames per block when the sources are drained through next() (analysis banks bring their own block_frames())
@@ -66,7 +65,7 @@ class AcousticEchoCancellationNode_ : public VectorComplexFeatureStream, public 
   PinnedBuffer hV_, hA_;
   std::vector<float> Ehost_, dense_;              // host mirror of the block [K][Ts_]; its dense copy [K][T_] for block()
   bool Ehost_valid_;
-  void *dR_, *dK_, *dSig_, *dHist_, *dDtd_;
+  DeviceBuffer dR_, dK_, dSig_, dHist_, dDtd_;     // the recursion's state (alloc_state_)
 };
 
 class NLMSAcousticEchoCancellationFeature : public AcousticEchoCancellationNode_ {

@@ -302,7 +302,6 @@ class SubbandGSCRLS : public SubbandGSC {
  public:
   SubbandGSCRLS(unsigned fftLen = 512, bool halfBandShift = false, float mu = 0.9, float sigma2 = 0.0,
                 const String& nm = "SubbandGSCRLS");
-  ~SubbandGSCRLS();
   virtual const gsl_vector_complex* next(int frame_no = -5);
   virtual const std::vector<float>& block(long& T);          // the adaptive recursion over the current block (not the static apply)
   virtual const void* device_block(long& T, long& T_stride);
@@ -328,9 +327,9 @@ class SubbandGSCRLS : public SubbandGSC {
   QuadraticConstraintType qctype_;
   unsigned long rls_version_;       // weights_version_ the cached block was computed with
   bool is_wa_updated_, have_P_;
-  void *dP_, *dW_, *dV_, *dSS_;     // device: P complex128 [K][N][N], w complex128 [K][N], wq complex128 [K][N], stream state
-  void* dCx_;                       // NC > 1: the further blocked directions, complex128 [K][NC-1][N] (btk_rls_*_nc)
-  void *dP0_, *dW0_, *dSS0_;        // the state at the start of the current block (a weight change before its first frame is served reruns it)
+  DeviceBuffer dP_, dW_, dV_, dSS_; // device: P complex128 [K][N][N], w complex128 [K][N], wq complex128 [K][N], stream state
+  DeviceBuffer dCx_;                // NC > 1: the further blocked directions, complex128 [K][NC-1][N] (btk_rls_*_nc)
+  DeviceBuffer dP0_, dW0_, dSS0_;   // the state at the start of the current block (a weight change before its first frame is served reruns it)
   unsigned long uploaded_version_;  // weights_version_ dV_ / dCx_ were built from
   bool block_ran_;
   DeviceBuffer dWs_;                // workspace of the recursion
@@ -373,7 +372,7 @@ class SubbandMVDR : public SubbandDS {
   int csvdc_not_converged() const { return csvdc_not_converged_; }    // bins of the last design with INFO != 0
  protected:
   void alloc_R_();
-  void* dR_;                        // device complex64 [K][N][N]
+  DeviceBuffer dR_;                 // device complex64 [K][N][N]
   std::vector<float> wmvdr_;        // complex64 [K][N]
   bool have_mvdr_;
   int fallbacks_;

@@ -4,7 +4,8 @@
 //   * every launch and every copy of a host thread's graphs is ordered on ONE non-NULL, non-blocking HIP stream
 //     (btk_node_stream(): the reference is single-threaded, one host thread drives one pipeline -- SURVEY 8(b) "Threading");
 //   * device and pinned buffers belong to the node that uses them and only ever GROW (DeviceBuffer / PinnedBuffer): once a
-//     stream has seen its largest block, a block costs no hipMalloc / hipHostMalloc / hipFree;
+//     stream has seen its largest block, a block costs no hipMalloc / hipHostMalloc / hipFree.  There is no other owner: a
+//     node's state is a DeviceBuffer member, a design-time temporary a local one, so every exit (a throwing one too) frees;
 //   * uploads come from pinned memory (the analysis banks keep their sample windows there), downloads go to pinned memory,
 //     both as hipMemcpyAsync on the node stream.
 // Everything declared here is defined in src/node_runtime.cc, together with the helpers the node files share (src/node_runtime.h:
@@ -21,6 +22,9 @@ void btk_node_synchronize();
 // allocations the node layer has made so far in this process: {hipMalloc, hipHostMalloc} (tests and the bench use the
 // difference across blocks to show that a steady-state block allocates nothing)
 void btk_node_alloc_counts(long* device_allocs, long* pinned_allocs);
+// device blocks the node layer holds right now: up where a DeviceBuffer gets a block from hipMalloc, down where it gives one
+// to hipFree (a test lets a node go and sees the count come back)
+long btk_node_live_device_blocks();
 // bytes the node layer has copied from the device to the host in this process since the last reset.  Every device-to-host copy
 // of a node reports its size with btk_node_count_d2h() (one relaxed atomic add): a graph that ends in a synthesis bank brings
 // nothing but its PCM back, and the difference across rounds shows it (tests/test_gpu_node_midstream.py)
@@ -38,6 +42,7 @@ void btk_node_timers_reset();
 class DeviceBuffer {
  public:
   DeviceBuffer() : p_(NULL), cap_(0) {}
+  explicit DeviceBuffer(size_t bytes) : p_(NULL), cap_(0) { ensure(bytes); }
   ~DeviceBuffer() { release(); }
   // at least `bytes` bytes; the contents are NOT kept when the buffer has to grow (it grows by half as much again at least)
   void* ensure(size_t bytes);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "stream/stream.h"
+#include "common/devmem.h"
 
 class MultiChannelWPEDereverberation : public Countable {
  public:
@@ -32,7 +33,7 @@ class MultiChannelWPEDereverberation : public Countable {
   const gsl_vector_complex* getOutput(unsigned channelX, int frame_no = -5) { (void)frame_no; return get_output(channelX); }
   void nextSpeaker() { next_speaker(); }
  private:
-  long snapshots_(void** dX);                    // drains the inputs: X complex64 [K][C][T] on the device, returns T
+  long snapshots_(DeviceBuffer& dX);              // drains the inputs: X complex64 [K][C][T] on the device, returns T
   void prepare_output_();
   std::vector<VectorComplexFeatureStreamPtr> sources_;
   const unsigned subbandsN_, channelsN_, lowerN_, upperN_, iterationsN_;
@@ -40,7 +41,7 @@ class MultiChannelWPEDereverberation : public Countable {
   unsigned lower_bw_, upper_bw_;
   bool estimated_;
   unsigned framesN_;
-  void* dG_;                                     // complex64 [C][K][C*L], zeros = a fresh object / next_speaker()
+  DeviceBuffer dG_;                              // complex64 [C][K][C*L], zeros = a fresh object / next_speaker()
   std::vector<float> out_;                       // complex64 [K][C][T] host mirror of the dereverberated utterance
   long T_;
   bool have_out_;

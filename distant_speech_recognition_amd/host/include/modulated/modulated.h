@@ -156,7 +156,7 @@ class OverSampledDFTSynthesisBank : public VectorFloatFeatureStream {
   bool no_stream_feature_;
   std::vector<float> ring_;                             // pushed frames, complex64 [W][K], oldest first (W = m R + R)
   long npushed_, npushed_at_next_;
-  void *dWin_, *dBlk_;                                  // source-less form: device window [K][W] complex64 and one output block
+  DeviceBuffer dWin_, dBlk_;                            // source-less form: device window [K][W] complex64 and one output block
   // rounds: the input window [history | this round's frames] complex64 [K][win_len_] and the output blocks, on the device; the
   // history of a device-resident source never visits the host (dev_hist_: hist_ is then empty and the window itself is the record)
   DeviceBuffer dRound_, dRoundNext_, dOut_;

@@ -21,6 +21,7 @@
 // Scan chunks sit on multiples of 64 of the stream's frame counter (include/btkhip.h), so blocks of 64, 128 or all frames give
 // the same samples.
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "stream/stream.h"
@@ -29,7 +30,6 @@
 
 class EnhancementBlockNode_ : public VectorComplexFeatureStream, public BlockSource {
  public:
-  virtual ~EnhancementBlockNode_();
   virtual const gsl_vector_complex* next(int frame_no = -5);
   virtual void reset();
   // frames per block when the sources are drained through next() (analysis banks bring their own block_frames())
@@ -84,7 +84,7 @@ class EnhancementBlockNode_ : public VectorComplexFeatureStream, public BlockSou
   long handed_, served_, fd0_;                  // block protocol mark; frames next() served; frames before the last reset()
   unsigned long version_;
   DeviceBuffer dX_, dY_, dTmp_, dCh_, dState_, dSnap_, dPeek_;
-  std::vector<DeviceBuffer*> dPcm_;
+  std::vector<std::unique_ptr<DeviceBuffer> > dPcm_;
   PinnedBuffer hX_;
   std::vector<float> Yhost_, dense_;
   bool Yhost_valid_;

@@ -59,7 +59,7 @@ class ZelinskiPostFilter : public VectorComplexFeatureStream, public BlockSource
   long T_;
   bool prepared_;
   unsigned long bf_version_;
-  void *dPhi_, *dPsi_, *dWl_;
+  DeviceBuffer dPhi_, dPsi_, dWl_;
   gsl_vector_complex* wp1_;
   long hist_start_;                         // stream index of the frame at which the density history last restarted (weights recomputed)
   SnapShotArrayPtr snapshot_array_;         // manual mode: multi-channel input kept current by the caller
@@ -110,13 +110,13 @@ class McCowanPostFilter : public ZelinskiPostFilter {
   void push_R_();
   float threshold_of_Rij_;
   unsigned nChanR_;
-  void* dR_;                        // device complex64 [K][N][N]
+  DeviceBuffer dR_;                 // device complex64 [K][N][N]
   std::vector<float> Rhost_;        // host mirror, complex64 [K][N][N]
   gsl_matrix_complex* Rview_;
   bool invR_computed_;
   double minSV_;
   unsigned fbinX1_;
-  void *dU_, *dV_;
+  DeviceBuffer dU_, dV_;
   DeviceBuffer dVsb_, dCsb_, dCvb_, dLamb_;
   String svd_rule_, lam_rule_;      // the rule in force / the one the kept Lambda was designed with
   bool lam_valid_;                  // dLamb_ matches R, the look direction (lam_version_) and the rule

@@ -4,7 +4,6 @@
 // that takes blocks (the synthesis bank) and mirrored to the host when a frame is asked for.  All of the recursion's state --
 // weights, covariances, noise variances, played history, the double-talk scalars -- stays in the device tensors btk_aec_process
 // updates, so results do not depend on where the blocks are cut.
-#include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include <cstring>
 
@@ -14,18 +13,11 @@
 namespace {
 
 using btknode::check_abi;
-using btknode::check_hip;
 using btknode::nstream;
 using btknode::d2h;
+using btknode::h2d_async;
+using btknode::dev_zero_async;
 using btknode::even_pitch;
-
-// local: unlike btknode::dev_alloc, the canceller's state blocks have never counted into btk_node_alloc_counts()
-void* dev_alloc(size_t bytes)
-{
-  void* p = NULL;
-  check_hip(hipMalloc(&p, bytes ? bytes : 16), "hipMalloc");
-  return p;
-}
 
 }  // namespace
 
@@ -34,8 +26,7 @@ AcousticEchoCancellationNode_::AcousticEchoCancellationNode_(int kind, const Vec
                                                              const double* params8, const String& nm)
     : VectorComplexFeatureStream(played->size(), nm), kind_(kind), played_(played), recorded_(recorded), pbank_(NULL), rbank_(NULL),
       fftLen_(played->size()), sampleN_(sampleN), block_frames_(btk_default_block_frames()), prepared_(false), ended_(false),
-      state_ready_(false), base_(0), T_(0), Ts_(0), block_frame_arg_(-5), Ehost_valid_(false), dR_(NULL), dK_(NULL), dSig_(NULL),
-      dHist_(NULL), dDtd_(NULL)
+      state_ready_(false), base_(0), T_(0), Ts_(0), block_frame_arg_(-5), Ehost_valid_(false)
 {
   if (recorded->size() != fftLen_)
     throw jdimension_error("%s: the played and the recorded stream differ in size (%d vs. %d)\n", nm.c_str(), (int)fftLen_, (int)recorded->size());
@@ -50,23 +41,17 @@ AcousticEchoCancellationNode_::AcousticEchoCancellationNode_(int kind, const Vec
   if (!pbank_ || !rbank_) { pbank_ = NULL; rbank_ = NULL; }
 }
 
-AcousticEchoCancellationNode_::~AcousticEchoCancellationNode_()
-{
-  void* p[5] = {dR_, dK_, dSig_, dHist_, dDtd_};
-  for (int i = 0; i < 5; i++) if (p[i]) (void)hipFree(p[i]);
-}
-
 void AcousticEchoCancellationNode_::alloc_state_()
 {
   if (state_ready_) return;
   const size_t K = fftLen_ / 2 + 1, P = sampleN_;
-  dR_ = dev_alloc(sizeof(double) * 2 * K * P);
-  dK_ = dev_alloc(sizeof(double) * 2 * K * P * P);
-  dSig_ = dev_alloc(sizeof(double) * K);
-  dHist_ = dev_alloc(sizeof(double) * 2 * K * P);
-  dDtd_ = dev_alloc(sizeof(double) * 4);
-  check_abi(btk_aec_init(kind_, params_, 1, (int)fftLen_, (int)sampleN_, dR_, dK_, static_cast<double*>(dSig_), dHist_,
-                         static_cast<double*>(dDtd_), nstream()));
+  dR_.ensure(sizeof(double) * 2 * K * P);
+  dK_.ensure(sizeof(double) * 2 * K * P * P);
+  dSig_.ensure(sizeof(double) * K);
+  dHist_.ensure(sizeof(double) * 2 * K * P);
+  dDtd_.ensure(sizeof(double) * 4);
+  check_abi(btk_aec_init(kind_, params_, 1, (int)fftLen_, (int)sampleN_, dR_.get(), dK_.get(), static_cast<double*>(dSig_.get()),
+                         dHist_.get(), static_cast<double*>(dDtd_.get()), nstream()));
   state_ready_ = true;
 }
 
@@ -99,7 +84,7 @@ bool AcousticEchoCancellationNode_::load_from_banks_(long& Tn)
     const long L = (b->blocks_pulled() - b0) * D;               // (samples past the end of an ended source read as zeros)
     float* dp = static_cast<float*>(dPcm[i]->ensure(sizeof(float) * (L > 0 ? L : 1)));
     void* dx = dX[i]->ensure(sizeof(float) * 2 * K * Ts);
-    if (L > 0) check_hip(hipMemcpyAsync(dp, b->window(b0), sizeof(float) * L, hipMemcpyHostToDevice, nstream()), "hipMemcpyAsync H2D");
+    if (L > 0) h2d_async(dp, b->window(b0), sizeof(float) * L);
     check_abi(btk_fb_analysis(b->plan(), dp, L > 0 ? L : 0, L > 0 ? L : 1, 1, 1, dx, Ts, f0 - b0, Tn, nstream()));
   }
   btk_node_synchronize();                                       // the windows move when the banks release what is done
@@ -140,8 +125,8 @@ bool AcousticEchoCancellationNode_::load_by_next_(long& Tn)
     }
   void* dv = dV_.ensure(sizeof(float) * 2 * K * Ts);
   void* da = dA_.ensure(sizeof(float) * 2 * K * Ts);
-  check_hip(hipMemcpyAsync(dv, hv, sizeof(float) * 2 * K * Ts, hipMemcpyHostToDevice, nstream()), "hipMemcpyAsync H2D");
-  check_hip(hipMemcpyAsync(da, ha, sizeof(float) * 2 * K * Ts, hipMemcpyHostToDevice, nstream()), "hipMemcpyAsync H2D");
+  h2d_async(dv, hv, sizeof(float) * 2 * K * Ts);
+  h2d_async(da, ha, sizeof(float) * 2 * K * Ts);
   btk_node_synchronize();                                       // the pinned rows are rewritten by the next block
   Tn = T; Ts_ = Ts;
   return true;
@@ -157,8 +142,8 @@ bool AcousticEchoCancellationNode_::load_block_(long frame_arg)
   void* de = dE_.ensure(sizeof(float) * 2 * K * Ts_);
   // explicit frame numbers count up from the block's first frame; a default-argument caller hands -5 to every frame (aec.cc:902)
   const long fn0 = frame_arg >= 0 ? f0 : frame_arg;
-  check_abi(btk_aec_process(kind_, params_, dV_.get(), dA_.get(), de, NULL, 1, (int)fftLen_, (int)sampleN_, Ts_, Tn, fn0, dR_, dK_,
-                            static_cast<double*>(dSig_), dHist_, static_cast<double*>(dDtd_), nstream()));
+  check_abi(btk_aec_process(kind_, params_, dV_.get(), dA_.get(), de, NULL, 1, (int)fftLen_, (int)sampleN_, Ts_, Tn, fn0, dR_.get(),
+                            dK_.get(), static_cast<double*>(dSig_.get()), dHist_.get(), static_cast<double*>(dDtd_.get()), nstream()));
   base_ = f0; T_ = Tn; block_frame_arg_ = frame_arg >= 0 ? 0 : frame_arg;
   Ehost_valid_ = false; prepared_ = true;
   return true;
@@ -207,7 +192,7 @@ void AcousticEchoCancellationNode_::reset()
   // aec.h:41,78: the one-tap filters zero their weights (the Kalman filter keeps sigma2_v and K); aec.h:111-114: the block
   // filters reset their sources only
   if (kind_ < 2 && state_ready_)
-    check_hip(hipMemsetAsync(dR_, 0, sizeof(double) * 2 * (fftLen_ / 2 + 1) * sampleN_, nstream()), "hipMemsetAsync");
+    dev_zero_async(dR_.get(), sizeof(double) * 2 * (fftLen_ / 2 + 1) * sampleN_);
 }
 
 void AcousticEchoCancellationNode_::ensure_first_(long frame_arg)
@@ -255,7 +240,7 @@ std::vector<double> AcousticEchoCancellationNode_::filter_coefficients(unsigned 
   if (fbinX > fftLen_ / 2) throw jindex_error("%s: state is kept for the bins 0..%d (asked for %d)\n", name().c_str(), (int)(fftLen_ / 2), (int)fbinX);
   alloc_state_();
   std::vector<double> r(2 * (size_t)sampleN_);
-  d2h(r.data(), static_cast<const double*>(dR_) + 2 * (size_t)fbinX * sampleN_, sizeof(double) * r.size());
+  d2h(r.data(), static_cast<const double*>(dR_.get()) + 2 * (size_t)fbinX * sampleN_, sizeof(double) * r.size());
   return r;
 }
 
@@ -264,7 +249,7 @@ std::vector<double> AcousticEchoCancellationNode_::state_covariance(unsigned fbi
   if (fbinX > fftLen_ / 2) throw jindex_error("%s: state is kept for the bins 0..%d (asked for %d)\n", name().c_str(), (int)(fftLen_ / 2), (int)fbinX);
   alloc_state_();
   std::vector<double> r(2 * (size_t)sampleN_ * sampleN_);
-  d2h(r.data(), static_cast<const double*>(dK_) + 2 * (size_t)fbinX * sampleN_ * sampleN_, sizeof(double) * r.size());
+  d2h(r.data(), static_cast<const double*>(dK_.get()) + 2 * (size_t)fbinX * sampleN_ * sampleN_, sizeof(double) * r.size());
   return r;
 }
 
@@ -273,7 +258,7 @@ double AcousticEchoCancellationNode_::observation_noise_variance(unsigned fbinX)
   if (fbinX > fftLen_ / 2) throw jindex_error("%s: state is kept for the bins 0..%d (asked for %d)\n", name().c_str(), (int)(fftLen_ / 2), (int)fbinX);
   alloc_state_();
   double v = 0.0;
-  d2h(&v, static_cast<const double*>(dSig_) + fbinX, sizeof(double));
+  d2h(&v, static_cast<const double*>(dSig_.get()) + fbinX, sizeof(double));
   return v;
 }
 

@@ -15,6 +15,7 @@ using btknode::check_hip;
 using btknode::nstream;
 using btknode::d2h;
 using btknode::h2d;
+using btknode::dev_zero_async;
 
 }  // namespace
 
@@ -231,7 +232,7 @@ KimITDThresholdEstimator::~KimITDThresholdEstimator()
 }
 
 size_t KimITDThresholdEstimator::state_bytes_() const { return sums_.state_bytes(); }
-void KimITDThresholdEstimator::init_state_(void* d) { check_hip(hipMemsetAsync(d, 0, state_bytes_(), nstream()), "hipMemsetAsync"); }
+void KimITDThresholdEstimator::init_state_(void* d) { dev_zero_async(d, state_bytes_()); }
 
 void KimITDThresholdEstimator::launch_(const void* dX, void* dOut, long Ts, long t0, long t1, long)
 {
@@ -247,7 +248,7 @@ void KimITDThresholdEstimator::reset()
 {
   EnhancementBlockNode_::reset();
   void* st = begin_switch_();                                   // (:416-425) the sums and nSamples_ go
-  check_hip(hipMemsetAsync(st, 0, state_bytes_(), nstream()), "hipMemsetAsync");
+  dev_zero_async(st, state_bytes_());
   end_switch_();
   cost_func_computed_ = false;
 }
@@ -313,7 +314,7 @@ FDIIDThresholdEstimator::~FDIIDThresholdEstimator()
 }
 
 size_t FDIIDThresholdEstimator::state_bytes_() const { return sums_.state_bytes(); }
-void FDIIDThresholdEstimator::init_state_(void* d) { check_hip(hipMemsetAsync(d, 0, state_bytes_(), nstream()), "hipMemsetAsync"); }
+void FDIIDThresholdEstimator::init_state_(void* d) { dev_zero_async(d, state_bytes_()); }
 
 void FDIIDThresholdEstimator::launch_(const void* dX, void* dOut, long Ts, long t0, long t1, long)
 {
@@ -329,7 +330,7 @@ void FDIIDThresholdEstimator::reset()
 {
   EnhancementBlockNode_::reset();
   void* st = begin_switch_();
-  check_hip(hipMemsetAsync(st, 0, state_bytes_(), nstream()), "hipMemsetAsync");
+  dev_zero_async(st, state_bytes_());
   end_switch_();
   cost_func_computed_ = false;
 }

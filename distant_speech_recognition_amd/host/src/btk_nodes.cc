@@ -709,7 +709,7 @@ OverSampledDFTSynthesisBank::OverSampledDFTSynthesisBank(VectorComplexFeatureStr
     : VectorFloatFeatureStream(M >> r, nm), samp_(samp), M_(M), m_(m), r_(r), D_(M >> r), gain_(gainFactor), plan_(NULL),
       nblocks_(0), blk_base_(0), prepared_(false), src_ended_(false), block_frames_(btk_default_block_frames()), hist_len_(0),
       frames_in_(0), cur_T_(0), bsrc_(NULL), src_version_(0), no_stream_feature_(false), npushed_(0), npushed_at_next_(0),
-      dWin_(NULL), dBlk_(NULL), win_len_(0), win_pitch_(0), dev_hist_(false), carry_cols_(0), prev_nblocks_(0)
+      win_len_(0), win_pitch_(0), dev_hist_(false), carry_cols_(0), prev_nblocks_(0)
 {
   init_(prototype, delayCompensationType);
 }
@@ -719,7 +719,7 @@ OverSampledDFTSynthesisBank::OverSampledDFTSynthesisBank(gsl_vector* prototype, 
     : VectorFloatFeatureStream(M >> r, nm), samp_(NULL), M_(M), m_(m), r_(r), D_(M >> r), gain_(gainFactor), plan_(NULL),
       nblocks_(0), blk_base_(0), prepared_(false), src_ended_(false), block_frames_(btk_default_block_frames()), hist_len_(0),
       frames_in_(0), cur_T_(0), bsrc_(NULL), src_version_(0), no_stream_feature_(true), npushed_(0), npushed_at_next_(0),
-      dWin_(NULL), dBlk_(NULL), win_len_(0), win_pitch_(0), dev_hist_(false), carry_cols_(0), prev_nblocks_(0)
+      win_len_(0), win_pitch_(0), dev_hist_(false), carry_cols_(0), prev_nblocks_(0)
 {
   init_(prototype, delayCompensationType);
 }
@@ -733,7 +733,7 @@ void OverSampledDFTSynthesisBank::init_(gsl_vector* prototype, unsigned delayCom
   check_abi(btk_fb_create(&plan_, (int)M_, (int)m_, (int)r_, (int)delayCompensationType, 1, g.data()));
 }
 
-OverSampledDFTSynthesisBank::~OverSampledDFTSynthesisBank() { btk_fb_destroy(plan_); dev_free(dWin_); dev_free(dBlk_); }
+OverSampledDFTSynthesisBank::~OverSampledDFTSynthesisBank() { btk_fb_destroy(plan_); }
 
 // Rows of a round's input window are win_pitch_ frames apart: the next even number (even_pitch, node_runtime.h).
 
@@ -941,10 +941,10 @@ const gsl_vector_float* OverSampledDFTSynthesisBank::next_pushed_()
       win[2 * ((size_t)k * Lw + i) + 1] = ring_[2 * ((size_t)q * K + k) + 1];
     }
   }
-  if (!dWin_) { dWin_ = dev_alloc(sizeof(float) * 2 * K * W); dBlk_ = dev_alloc(sizeof(float) * D_); }
-  h2d(dWin_, win.data(), sizeof(float) * win.size());
-  check_abi(btk_fb_synthesis(plan_, dWin_, Lw, Lw, 1, (float*)dBlk_, D_, Lw - 1 - pd, 1, nstream()));
-  d2h(vector_->data, dBlk_, sizeof(float) * D_);
+  if (!dWin_.get()) { dWin_.ensure(sizeof(float) * 2 * K * W); dBlk_.ensure(sizeof(float) * D_); }
+  h2d(dWin_.get(), win.data(), sizeof(float) * win.size());
+  check_abi(btk_fb_synthesis(plan_, dWin_.get(), Lw, Lw, 1, (float*)dBlk_.get(), D_, Lw - 1 - pd, 1, nstream()));
+  d2h(vector_->data, dBlk_.get(), sizeof(float) * D_);
   if (gain_ > 1) for (unsigned i = 0; i < D_; i++) vector_->data[i] *= (float)gain_;
   npushed_at_next_ = npushed_;
   increment_();
@@ -1953,7 +1953,7 @@ void SubbandMVDR::set_svd_rule(const String& rule)
 }
 
 SubbandMVDR::SubbandMVDR(unsigned fftLen, bool halfBandShift, const String& nm)
-    : SubbandDS(fftLen, halfBandShift, nm), dR_(NULL), have_mvdr_(false), fallbacks_(0), svd_rule_(default_svd_rule()),
+    : SubbandDS(fftLen, halfBandShift, nm), have_mvdr_(false), fallbacks_(0), svd_rule_(default_svd_rule()),
       csvdc_not_converged_(0), wm_view_(gsl_vector_complex_calloc(1)), R_view_(NULL)
 {
   if (halfBandShift) {                                       // reference beamformer.cc:2283-2285
@@ -1961,42 +1961,41 @@ SubbandMVDR::SubbandMVDR(unsigned fftLen, bool halfBandShift, const String& nm)
     throw jallocation_error("halfBandShift==true is not yet supported\n");
   }
 }
-SubbandMVDR::~SubbandMVDR() { dev_free(dR_); gsl_vector_complex_free(wm_view_); gsl_matrix_complex_free(R_view_); }
+SubbandMVDR::~SubbandMVDR() { gsl_vector_complex_free(wm_view_); gsl_matrix_complex_free(R_view_); }
 
 void SubbandMVDR::divide_all_nondiagonal_elements(float mu)
 {
-  if (!dR_) throw j_error("Construct first a noise covariance matrix\n");
-  check_abi(btk_mvdr_divide_nondiagonal(dR_, (int)(fftLen2_ + 1), (int)chanN(), mu, nstream()));
+  if (!dR_.get()) throw j_error("Construct first a noise covariance matrix\n");
+  check_abi(btk_mvdr_divide_nondiagonal(dR_.get(), (int)(fftLen2_ + 1), (int)chanN(), mu, nstream()));
 }
 
 void SubbandMVDR::divide_nondiagonal_elements(unsigned fbinX, float mu)
 {
-  if (!dR_) throw j_error("Construct first a noise covariance matrix\n");
+  if (!dR_.get()) throw j_error("Construct first a noise covariance matrix\n");
   if (fbinX > fftLen2_) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)fftLen2_);
   const unsigned N = chanN();
-  check_abi(btk_mvdr_divide_nondiagonal(static_cast<float*>(dR_) + (size_t)fbinX * 2 * N * N, 1, (int)N, mu, nstream()));
+  check_abi(btk_mvdr_divide_nondiagonal(static_cast<float*>(dR_.get()) + (size_t)fbinX * 2 * N * N, 1, (int)N, mu, nstream()));
 }
 
 const gsl_matrix_complex* SubbandMVDR::noise_spatial_spectral_matrix(unsigned fbinX)
 {
-  if (!dR_) return NULL;                                       // the reference returns its NULL R_[fbinX]
+  if (!dR_.get()) return NULL;                                 // the reference returns its NULL R_[fbinX]
   if (fbinX > fftLen2_) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)fftLen2_);
   const unsigned N = chanN();
   if (!R_view_ || R_view_->size1 != N) { gsl_matrix_complex_free(R_view_); R_view_ = gsl_matrix_complex_alloc(N, N); }
   std::vector<float> r((size_t)2 * N * N);
   nsync();
-  d2h(r.data(), static_cast<float*>(dR_) + (size_t)fbinX * 2 * N * N, sizeof(float) * r.size());
+  d2h(r.data(), static_cast<float*>(dR_.get()) + (size_t)fbinX * 2 * N * N, sizeof(float) * r.size());
   for (size_t i = 0; i < (size_t)2 * N * N; i++) R_view_->data[i] = r[i];
   return R_view_;
 }
-void SubbandMVDR::clear_channel() { SubbandDS::clear_channel(); dev_free(dR_); dR_ = NULL; have_mvdr_ = false; }
+void SubbandMVDR::clear_channel() { SubbandDS::clear_channel(); dR_.release(); have_mvdr_ = false; }
 
 void SubbandMVDR::alloc_R_()
 {
-  if (dR_) return;
+  if (dR_.get()) return;
   const size_t n = (size_t)2 * (fftLen2_ + 1) * chanN() * chanN();
-  dR_ = dev_alloc(sizeof(float) * n);
-  dev_zero_async(dR_, sizeof(float) * n);
+  dev_zero_async(dR_.ensure(sizeof(float) * n), sizeof(float) * n);
 }
 
 bool SubbandMVDR::set_noise_spatial_spectral_matrix(unsigned fbinX, gsl_matrix_complex* Rnn)
@@ -2012,7 +2011,7 @@ bool SubbandMVDR::set_noise_spatial_spectral_matrix(unsigned fbinX, gsl_matrix_c
       const gsl_complex z = gsl_matrix_complex_get(Rnn, a, b);
       r[2 * ((size_t)a * N + b)] = (float)GSL_REAL(z); r[2 * ((size_t)a * N + b) + 1] = (float)GSL_IMAG(z);
     }
-  h2d(static_cast<float*>(dR_) + (size_t)fbinX * 2 * N * N, r.data(), sizeof(float) * r.size());
+  h2d(static_cast<float*>(dR_.get()) + (size_t)fbinX * 2 * N * N, r.data(), sizeof(float) * r.size());
   return true;
 }
 
@@ -2024,75 +2023,71 @@ bool SubbandMVDR::set_diffuse_noise_model(const gsl_matrix* micPositions, float 
   alloc_R_();
   std::vector<float> mp((size_t)3 * N);
   for (unsigned a = 0; a < N; a++) for (int j = 0; j < 3; j++) mp[3 * a + j] = (float)gsl_matrix_get(micPositions, a, j);
-  void* dmp = dev_alloc(sizeof(float) * mp.size());
-  h2d(dmp, mp.data(), sizeof(float) * mp.size());
-  check_abi(btk_mvdr_diffuse_model((const float*)dmp, (int)N, (int)fftLen_, samplerate, sspeed, dR_, nstream()));
+  DeviceBuffer dmp(sizeof(float) * mp.size());
+  h2d(dmp.get(), mp.data(), sizeof(float) * mp.size());
+  check_abi(btk_mvdr_diffuse_model((const float*)dmp.get(), (int)N, (int)fftLen_, samplerate, sspeed, dR_.get(), nstream()));
   nsync();
-  dev_free(dmp);
   return true;
 }
 
 void SubbandMVDR::set_all_diagonal_loading(float diagonalWeight)
 {
-  if (!dR_) throw j_error("Construct first a noise covariance matrix\n");
-  check_abi(btk_mvdr_diagonal_loading(dR_, (int)(fftLen2_ + 1), (int)chanN(), diagonalWeight, nstream()));
+  if (!dR_.get()) throw j_error("Construct first a noise covariance matrix\n");
+  check_abi(btk_mvdr_diagonal_loading(dR_.get(), (int)(fftLen2_ + 1), (int)chanN(), diagonalWeight, nstream()));
 }
 
 void SubbandMVDR::set_diagonal_looading(unsigned fbinX, float diagonalWeight)
 {
-  if (!dR_) throw j_error("Construct first a noise covariance matrix\n");
+  if (!dR_.get()) throw j_error("Construct first a noise covariance matrix\n");
   if (fbinX > fftLen2_) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)fftLen2_);
   const unsigned N = chanN();
-  check_abi(btk_mvdr_diagonal_loading(static_cast<float*>(dR_) + (size_t)fbinX * 2 * N * N, 1, (int)N, diagonalWeight, nstream()));
+  check_abi(btk_mvdr_diagonal_loading(static_cast<float*>(dR_.get()) + (size_t)fbinX * 2 * N * N, 1, (int)N, diagonalWeight, nstream()));
 }
 
 bool SubbandMVDR::calc_mvdr_weights(float, float dThreshold, bool)
 {
-  if (!dR_) throw jallocation_error("Set a spatial spectral matrix before calling calc_mvdr_weights()\n");
+  if (!dR_.get()) throw jallocation_error("Set a spatial spectral matrix before calling calc_mvdr_weights()\n");
   if (!bfweight_) throw j_error("call calc_array_manifold_vectorsX() once\n");
   const unsigned N = chanN(), K = fftLen2_ + 1;
   std::vector<float> d;
   alignment_vector(true, d);
-  void* dD = dev_alloc(sizeof(float) * d.size());
-  void* dW = dev_alloc(sizeof(float) * d.size());
+  DeviceBuffer dDb(sizeof(float) * d.size()), dWb(sizeof(float) * d.size());
+  void *const dD = dDb.get(), *const dW = dWb.get();
   if (svd_rule_ == "linpack_full") {
     // the reference's own float32 SVD pseudo-inverse and float64 weight step on every bin (beamformer.cc:232-289, 2372-2397):
     // no Cholesky solve, no fall-back; the identity where pseudoinverse() returns false
     int counts[2] = {0, 0};
-    void* dcnt = dev_alloc(sizeof(int) * 2);
-    void* fs = dev_alloc((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
+    DeviceBuffer dcnt(sizeof(int) * 2), fs((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
     h2d(dD, d.data(), sizeof(float) * d.size());
-    dev_zero_async(dcnt, sizeof(int) * 2);
-    check_abi(btk_mvdr_linpack_full(dR_, dD, dW, NULL, (int)K, (int)N, 0, 0, 1, dThreshold, (int*)dcnt, fs, nstream()));
+    dev_zero_async(dcnt.get(), sizeof(int) * 2);
+    check_abi(btk_mvdr_linpack_full(dR_.get(), dD, dW, NULL, (int)K, (int)N, 0, 0, 1, dThreshold, (int*)dcnt.get(), fs.get(), nstream()));
     nsync();
-    d2h(counts, dcnt, sizeof(counts));
+    d2h(counts, dcnt.get(), sizeof(counts));
     csvdc_not_converged_ = counts[0];
     fallbacks_ = counts[0] + counts[1];
     wmvdr_.resize(d.size());
     d2h(wmvdr_.data(), dW, sizeof(float) * wmvdr_.size());
-    dev_free(dD); dev_free(dW); dev_free(dcnt); dev_free(fs);
     have_mvdr_ = true;
     weights_version_++;
     return true;
   }
-  void* dfb = dev_alloc(sizeof(int));
+  DeviceBuffer dfb(sizeof(int)), scratch;
   const long sbytes = btk_mvdr_scratch_bytes((int)K, (int)N);                   // (only the panel solver copies R)
-  void* scratch = sbytes ? dev_alloc((size_t)sbytes) : NULL;
-  void* dflags = dev_alloc(sizeof(int) * K);
+  if (sbytes) scratch.ensure((size_t)sbytes);
+  DeviceBuffer dflagsb(sizeof(int) * K);
+  void* const dflags = dflagsb.get();
   h2d(dD, d.data(), sizeof(float) * d.size());
-  dev_zero_async(dfb, sizeof(int));
-  check_abi(btk_mvdr_weights_flags(dR_, dD, dW, (int)K, (int)N, 0, dThreshold, scratch, (int*)dfb, (int*)dflags, nstream()));
+  dev_zero_async(dfb.get(), sizeof(int));
+  check_abi(btk_mvdr_weights_flags(dR_.get(), dD, dW, (int)K, (int)N, 0, dThreshold, scratch.get(), (int*)dfb.get(), (int*)dflags, nstream()));
   int rule_counts[2] = {0, 0};
   if (svd_rule_ == "linpack") {
     // pseudoinverse() returns false where the reference's float32 csvdc gives INFO != 0 or a singular value under the
     // threshold -> identity (beamformer.cc:253-270, 2379-2384); those bins also leave the fall-back's list
-    void* dcnt = dev_alloc(sizeof(int) * 2);
-    void* rs = dev_alloc((size_t)btk_mvdr_linpack_rule_scratch_bytes((int)K, (int)N));
-    dev_zero_async(dcnt, sizeof(int) * 2);
-    check_abi(btk_mvdr_linpack_rule(dR_, dD, dW, NULL, (int)K, (int)N, 0, 0, 1, dThreshold, (int*)dflags, (int*)dcnt, rs, nstream()));
+    DeviceBuffer dcnt(sizeof(int) * 2), rs((size_t)btk_mvdr_linpack_rule_scratch_bytes((int)K, (int)N));
+    dev_zero_async(dcnt.get(), sizeof(int) * 2);
+    check_abi(btk_mvdr_linpack_rule(dR_.get(), dD, dW, NULL, (int)K, (int)N, 0, 0, 1, dThreshold, (int*)dflags, (int*)dcnt.get(), rs.get(), nstream()));
     nsync();
-    d2h(rule_counts, dcnt, sizeof(rule_counts));
-    dev_free(dcnt); dev_free(rs);
+    d2h(rule_counts, dcnt.get(), sizeof(rule_counts));
   }
   nsync();
   csvdc_not_converged_ = rule_counts[0];
@@ -2102,11 +2097,10 @@ bool SubbandMVDR::calc_mvdr_weights(float, float dThreshold, bool)
   for (unsigned k = 0; k < K; ++k) stopped += hflags[k] != 0;
   fallbacks_ = 0;
   if (stopped > 0)     // bins the Cholesky solve gave up on and the rule above left open: the pseudo-inverse (beamformer.cc:232-289)
-    check_abi(btk_mvdr_pinv_fallback(dR_, dD, dW, (int)K, (int)N, 0, dThreshold, (const int*)dflags, &fallbacks_, nstream()));
+    check_abi(btk_mvdr_pinv_fallback(dR_.get(), dD, dW, (int)K, (int)N, 0, dThreshold, (const int*)dflags, &fallbacks_, nstream()));
   fallbacks_ += rule_counts[0] + rule_counts[1];
   wmvdr_.resize(d.size());
   d2h(wmvdr_.data(), dW, sizeof(float) * wmvdr_.size());
-  dev_free(dD); dev_free(dW); dev_free(dfb); dev_free(dflags); dev_free(scratch);
   have_mvdr_ = true;
   weights_version_++;
   return true;
@@ -2215,7 +2209,7 @@ void SubbandMVDRGSC::effective_weights(std::vector<float>& w)
 ZelinskiPostFilter::ZelinskiPostFilter(VectorComplexFeatureStreamPtr& output, unsigned fftLen, double alpha, int type,
                                        int minFrames, const String& nm)
     : VectorComplexFeatureStream(fftLen, nm), fftLen_(fftLen), samp_(output), type_((PostfilterType)type), alpha_(alpha),
-      min_frames_(minFrames), has_bf_ptr_(false), Yhost_valid_(false), T_(0), prepared_(false), bf_version_(0), dPhi_(NULL), dPsi_(NULL), dWl_(NULL),
+      min_frames_(minFrames), has_bf_ptr_(false), Yhost_valid_(false), T_(0), prepared_(false), bf_version_(0),
       wp1_(gsl_vector_complex_calloc(fftLen)), hist_start_(0), own_weights_(NULL), manual_frames_(0), base_(0), carry_state_(false),
       csd_dev_n_(0), handed_(-1)
 {
@@ -2225,7 +2219,7 @@ ZelinskiPostFilter::ZelinskiPostFilter(VectorComplexFeatureStreamPtr& output, un
 ZelinskiPostFilter::~ZelinskiPostFilter()
 {
   if (has_bf_ptr_ && bf_ptr_->beamformer_weight_object()) bf_ptr_->beamformer_weight_object()->clear_csd_provider(this);
-  dev_free(dPhi_); dev_free(dPsi_); dev_free(dWl_); gsl_vector_complex_free(wp1_);
+  gsl_vector_complex_free(wp1_);
   delete own_weights_;
 }
 
@@ -2298,14 +2292,12 @@ void ZelinskiPostFilter::csd_state_(long t, std::vector<float>& R)
     tail = csd_frame_weights(t, lo, base_, alpha_, fw);
     void* dX = bf_ptr_->device_snapshots();
     const long Tstride = bf_ptr_->num_frames();
-    void* dF = dev_alloc(sizeof(float) * Tn);
-    void* dR = dev_alloc(sizeof(float) * R.size());
-    h2d(dF, fw.data(), sizeof(float) * Tn);
-    dev_zero_async(dR, sizeof(float) * R.size());
-    check_abi(btk_cov_accumulate(dX, NULL, (const float*)dF, dR, 1, (int)K, (int)N, Tstride, Tn, 0, nstream()));
+    DeviceBuffer dF(sizeof(float) * Tn), dR(sizeof(float) * R.size());
+    h2d(dF.get(), fw.data(), sizeof(float) * Tn);
+    dev_zero_async(dR.get(), sizeof(float) * R.size());
+    check_abi(btk_cov_accumulate(dX, NULL, (const float*)dF.get(), dR.get(), 1, (int)K, (int)N, Tstride, Tn, 0, nstream()));
     nsync();
-    d2h(R.data(), dR, sizeof(float) * R.size());
-    dev_free(dF); dev_free(dR);
+    d2h(R.data(), dR.get(), sizeof(float) * R.size());
   }
   if (hist_start_ < base_ && csd_carry_.size() == R.size() && tail != 0.0)
     for (size_t i = 0; i < R.size(); i++) R[i] += (float)(tail * csd_carry_[i]);
@@ -2403,26 +2395,24 @@ const gsl_vector_complex* ZelinskiPostFilter::next_manual_(int frame_no)
         }
       }
   }
-  if (!dPhi_) {
-    dPhi_ = dev_alloc(sizeof(float) * 2 * K); dPsi_ = dev_alloc(sizeof(float) * K); dWl_ = dev_alloc(sizeof(float) * K);
-    dev_zero_async(dPhi_, sizeof(float) * 2 * K);
-    dev_zero_async(dPsi_, sizeof(float) * K);
-    dev_zero_async(dWl_, sizeof(float) * K);
+  if (!dPhi_.get()) {
+    dPhi_.ensure(sizeof(float) * 2 * K); dPsi_.ensure(sizeof(float) * K); dWl_.ensure(sizeof(float) * K);
+    dev_zero_async(dPhi_.get(), sizeof(float) * 2 * K);
+    dev_zero_async(dPsi_.get(), sizeof(float) * K);
+    dev_zero_async(dWl_.get(), sizeof(float) * K);
   }
-  void* dXf = dev_alloc(sizeof(float) * x.size());
-  void* dD = dev_alloc(sizeof(float) * d.size());
-  void* dY = dev_alloc(sizeof(float) * 2 * K);
-  void* dC = dev_alloc(sizeof(float) * 2 * K);
-  void* dE = dev_alloc(sizeof(float) * K);
+  // (per frame, as ever: this path is the reference's frame-by-frame use, not the block path)
+  DeviceBuffer bXf(sizeof(float) * x.size()), bD(sizeof(float) * d.size()), bY(sizeof(float) * 2 * K), bC(sizeof(float) * 2 * K),
+      bE(sizeof(float) * K);
+  void *const dXf = bXf.get(), *const dD = bD.get(), *const dY = bY.get(), *const dC = bC.get(), *const dE = bE.get();
   h2d(dXf, x.data(), sizeof(float) * x.size());
   h2d(dD, d.data(), sizeof(float) * d.size());
   check_abi(btk_bf_apply_stats(dD, dD, 0, dXf, dY, dC, (float*)dE, 1, (int)K, (int)N, 1, 1, nstream()));   // only C and E are used
   h2d(dY, y.data(), sizeof(float) * y.size());                                                        // the frame to filter is samp_'s
   check_abi(btk_zelinski_process(dY, dC, (const float*)dE, 1, (int)K, (int)N, 1, 1, alpha_, (int)type_, min_frames_,
-                                 manual_frames_, dPhi_, (float*)dPsi_, (float*)dWl_, nstream()));
+                                 manual_frames_, dPhi_.get(), (float*)dPsi_.get(), (float*)dWl_.get(), nstream()));
   nsync();
   d2h(y.data(), dY, sizeof(float) * y.size());
-  dev_free(dXf); dev_free(dD); dev_free(dY); dev_free(dC); dev_free(dE);
   for (unsigned k = 0; k < K; k++) {
     vector_->data[2 * k] = y[2 * k]; vector_->data[2 * k + 1] = y[2 * k + 1];
     if (k > 0 && k < fftLen_ / 2) { vector_->data[2 * (fftLen_ - k)] = y[2 * k]; vector_->data[2 * (fftLen_ - k) + 1] = -y[2 * k + 1]; }
@@ -2447,15 +2437,15 @@ void ZelinskiPostFilter::compute_(long from_frame)
   bf->effective_weights(w);
   bf->alignment_vector((type_ & TYPE_ZELINSKI2) != 0, d);
   const long Tn = T_ - from_frame;
-  const bool carry = carry_state_ && dPhi_ && bf_version_ == bf->weights_version();
+  const bool carry = carry_state_ && dPhi_.get() && bf_version_ == bf->weights_version();
   carry_state_ = false;
-  if (!dPhi_) { dPhi_ = dev_alloc(sizeof(float) * 2 * K); dPsi_ = dev_alloc(sizeof(float) * K); dWl_ = dev_alloc(sizeof(float) * K); }
+  if (!dPhi_.get()) { dPhi_.ensure(sizeof(float) * 2 * K); dPsi_.ensure(sizeof(float) * K); dWl_.ensure(sizeof(float) * K); }
   if (!carry) {
     // weights (re)computed: the CSD history restarts, the frame counter keeps counting; the following block
     // of the same stream instead continues from the densities the block before left on the device
-    dev_zero_async(dPhi_, sizeof(float) * 2 * K);
-    dev_zero_async(dPsi_, sizeof(float) * K);
-    dev_zero_async(dWl_, sizeof(float) * K);
+    dev_zero_async(dPhi_.get(), sizeof(float) * 2 * K);
+    dev_zero_async(dPsi_.get(), sizeof(float) * K);
+    dev_zero_async(dWl_.get(), sizeof(float) * K);
   }
   // node-owned blocks that only grow; the frames before from_frame keep what the pass before left in dYb_ (same block, same size)
   void* dY = dYb_.ensure(sizeof(float) * 2 * K * (T_ ? T_ : 1));
@@ -2473,7 +2463,7 @@ void ZelinskiPostFilter::compute_(long from_frame)
     float* Eo = static_cast<float*>(dE) + from_frame;
     check_abi(btk_bf_apply_stats(dW, dD, 0, Xo, Yo, Co, Eo, 1, (int)K, (int)N, T_, Tn, nstream()));
     check_abi(btk_zelinski_process(Yo, Co, Eo, 1, (int)K, (int)N, T_, Tn, alpha_, (int)type_, min_frames_, base_ + from_frame,
-                                   dPhi_, (float*)dPsi_, (float*)dWl_, nstream()));
+                                   dPhi_.get(), (float*)dPsi_.get(), (float*)dWl_.get(), nstream()));
   }
   Yhost_valid_ = false;
   bf_version_ = bf->weights_version();
@@ -2563,10 +2553,10 @@ void ZelinskiPostFilter::advance_to(long frame_idx)
 
 const gsl_vector_complex* ZelinskiPostFilter::postfilter_weights()
 {
-  if (!dWl_) return NULL;
+  if (!dWl_.get()) return NULL;
   const unsigned K = fftLen_ / 2 + 1;
   std::vector<float> wl(K);
-  d2h(wl.data(), dWl_, sizeof(float) * K);
+  d2h(wl.data(), dWl_.get(), sizeof(float) * K);
   for (unsigned k = 0; k < K; k++) {
     wp1_->data[2 * k] = wl[k]; wp1_->data[2 * k + 1] = 0.0;
     if (k > 0 && k < fftLen_ / 2) { wp1_->data[2 * (fftLen_ - k)] = wl[k]; wp1_->data[2 * (fftLen_ - k) + 1] = 0.0; }
@@ -2584,19 +2574,19 @@ void ZelinskiPostFilter::reset()
   is_end_ = false;
   prepared_ = false; Yhost_.clear(); Yhost_valid_ = false; T_ = 0; base_ = 0; carry_state_ = false; csd_carry_.clear(); csd_dev_n_ = 0;
   csd_manual_.clear(); manual_frames_ = 0; hist_start_ = 0; handed_ = -1;
-  if (!has_bf_ptr_ && dPhi_) {              // manual mode: the densities of the next utterance start from zero
+  if (!has_bf_ptr_ && dPhi_.get()) {        // manual mode: the densities of the next utterance start from zero
     const unsigned K = fftLen_ / 2 + 1;
-    dev_zero_async(dPhi_, sizeof(float) * 2 * K);
-    dev_zero_async(dPsi_, sizeof(float) * K);
-    dev_zero_async(dWl_, sizeof(float) * K);
+    dev_zero_async(dPhi_.get(), sizeof(float) * 2 * K);
+    dev_zero_async(dPsi_.get(), sizeof(float) * K);
+    dev_zero_async(dWl_.get(), sizeof(float) * K);
   }
 }
 
 // ================================================================================ McCowan / Lefkimmiatis
 McCowanPostFilter::McCowanPostFilter(VectorComplexFeatureStreamPtr& output, unsigned fftLen, double alpha, int type,
                                      int minFrames, float threshold, const String& nm)
-    : ZelinskiPostFilter(output, fftLen, alpha, type, minFrames, nm), threshold_of_Rij_(threshold), nChanR_(0), dR_(NULL),
-      Rview_(NULL), invR_computed_(false), minSV_(1.0e-8), fbinX1_(0), dU_(NULL), dV_(NULL), svd_rule_(default_svd_rule()),
+    : ZelinskiPostFilter(output, fftLen, alpha, type, minFrames, nm), threshold_of_Rij_(threshold), nChanR_(0),
+      Rview_(NULL), invR_computed_(false), minSV_(1.0e-8), fbinX1_(0), svd_rule_(default_svd_rule()),
       lam_valid_(false), lam_version_(0) {}
 
 void McCowanPostFilter::set_svd_rule(const String& rule)
@@ -2607,7 +2597,6 @@ void McCowanPostFilter::set_svd_rule(const String& rule)
 
 McCowanPostFilter::~McCowanPostFilter()
 {
-  dev_free(dR_); dev_free(dU_); dev_free(dV_);
   if (Rview_) gsl_matrix_complex_free(Rview_);
 }
 
@@ -2615,18 +2604,18 @@ void McCowanPostFilter::fetch_R_()
 {
   const unsigned K = fftLen_ / 2 + 1;
   Rhost_.resize((size_t)2 * K * nChanR_ * nChanR_);
-  if (dR_) d2h(Rhost_.data(), dR_, sizeof(float) * Rhost_.size());
+  if (dR_.get()) d2h(Rhost_.data(), dR_.get(), sizeof(float) * Rhost_.size());
 }
 void McCowanPostFilter::push_R_()
 {
-  h2d(dR_, Rhost_.data(), sizeof(float) * Rhost_.size());
+  h2d(dR_.get(), Rhost_.data(), sizeof(float) * Rhost_.size());
   invR_computed_ = false; lam_valid_ = false;
   prepared_ = false;
 }
 
 const gsl_matrix_complex* McCowanPostFilter::noise_spatial_spectral_matrix(unsigned fbinX)
 {
-  if (!dR_) return NULL;
+  if (!dR_.get()) return NULL;
   if (fbinX > fftLen_ / 2) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)(fftLen_ / 2));
   fetch_R_();
   const unsigned N = nChanR_;
@@ -2641,11 +2630,10 @@ bool McCowanPostFilter::set_noise_spatial_spectral_matrix(unsigned fbinX, gsl_ma
   if (Rnn->size1 != Rnn->size2) { fprintf(stderr, "The noise coherence matrix should be the square matrix\n"); return false; }
   if (fbinX > fftLen_ / 2) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)(fftLen_ / 2));
   const unsigned K = fftLen_ / 2 + 1, N = (unsigned)Rnn->size1;
-  if (!dR_ || nChanR_ != N) {
-    dev_free(dR_);
+  if (!dR_.get() || nChanR_ != N) {
+    dR_.release();                                  // (a fresh block of exactly this size, as ever)
     nChanR_ = N;
-    dR_ = dev_alloc(sizeof(float) * 2 * K * N * N);
-    dev_zero_async(dR_, sizeof(float) * 2 * K * N * N);
+    dev_zero_async(dR_.ensure(sizeof(float) * 2 * K * N * N), sizeof(float) * 2 * K * N * N);
   }
   fetch_R_();
   for (unsigned a = 0; a < N; a++)
@@ -2662,14 +2650,13 @@ bool McCowanPostFilter::set_diffuse_noise_model(const gsl_matrix* micPositions, 
 {
   const unsigned K = fftLen_ / 2 + 1, N = (unsigned)micPositions->size1;
   if (micPositions->size2 < 3) { fprintf(stderr, "The microphone positions should be described in the three dimensions\n"); return false; }
-  if (!dR_ || nChanR_ != N) { dev_free(dR_); nChanR_ = N; dR_ = dev_alloc(sizeof(float) * 2 * K * N * N); }
+  if (!dR_.get() || nChanR_ != N) { dR_.release(); nChanR_ = N; dR_.ensure(sizeof(float) * 2 * K * N * N); }
   std::vector<float> mp((size_t)3 * N);
   for (unsigned a = 0; a < N; a++) for (int j = 0; j < 3; j++) mp[3 * a + j] = (float)gsl_matrix_get(micPositions, a, j);
-  void* dmp = dev_alloc(sizeof(float) * mp.size());
-  h2d(dmp, mp.data(), sizeof(float) * mp.size());
-  check_abi(btk_mvdr_diffuse_model((const float*)dmp, (int)N, (int)fftLen_, (float)sampleRate, (float)sspeed, dR_, nstream()));
+  DeviceBuffer dmp(sizeof(float) * mp.size());
+  h2d(dmp.get(), mp.data(), sizeof(float) * mp.size());
+  check_abi(btk_mvdr_diffuse_model((const float*)dmp.get(), (int)N, (int)fftLen_, (float)sampleRate, (float)sspeed, dR_.get(), nstream()));
   nsync();
-  dev_free(dmp);
   invR_computed_ = false; lam_valid_ = false;
   prepared_ = false;
   return true;
@@ -2677,17 +2664,17 @@ bool McCowanPostFilter::set_diffuse_noise_model(const gsl_matrix* micPositions, 
 
 void McCowanPostFilter::set_all_diagonal_loading(float diagonalWeight)
 {
-  if (!dR_) throw j_error("Construct/set first a noise coherence matrix\n");
-  check_abi(btk_mvdr_diagonal_loading(dR_, (int)(fftLen_ / 2 + 1), (int)nChanR_, diagonalWeight, nstream()));
+  if (!dR_.get()) throw j_error("Construct/set first a noise coherence matrix\n");
+  check_abi(btk_mvdr_diagonal_loading(dR_.get(), (int)(fftLen_ / 2 + 1), (int)nChanR_, diagonalWeight, nstream()));
   invR_computed_ = false; lam_valid_ = false;
   prepared_ = false;
 }
 
 void McCowanPostFilter::set_diagonal_looading(unsigned fbinX, float diagonalWeight)
 {
-  if (!dR_) throw j_error("Construct/set first a noise coherence matrix\n");
+  if (!dR_.get()) throw j_error("Construct/set first a noise coherence matrix\n");
   if (fbinX > fftLen_ / 2) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)(fftLen_ / 2));
-  check_abi(btk_mvdr_diagonal_loading(static_cast<float*>(dR_) + (size_t)2 * fbinX * nChanR_ * nChanR_, 1, (int)nChanR_,
+  check_abi(btk_mvdr_diagonal_loading(static_cast<float*>(dR_.get()) + (size_t)2 * fbinX * nChanR_ * nChanR_, 1, (int)nChanR_,
                                       diagonalWeight, nstream()));
   invR_computed_ = false; lam_valid_ = false;
   prepared_ = false;
@@ -2695,7 +2682,7 @@ void McCowanPostFilter::set_diagonal_looading(unsigned fbinX, float diagonalWeig
 
 void McCowanPostFilter::divide_nondiagonal_elements(unsigned fbinX, float mu)
 {
-  if (!dR_) throw j_error("Construct/set first a noise coherence matrix\n");
+  if (!dR_.get()) throw j_error("Construct/set first a noise coherence matrix\n");
   if (fbinX > fftLen_ / 2) throw jindex_error("frequency bin %d is out of range: the matrices exist for bins 0..%d\n", (int)fbinX, (int)(fftLen_ / 2));
   fetch_R_();
   const unsigned N = nChanR_;
@@ -2717,7 +2704,7 @@ void McCowanPostFilter::divide_all_nondiagonal_elements(float mu)
 void McCowanPostFilter::compute_(long from_frame)
 {
   if (!has_bf_ptr_) throw j_error("set beamformer's weights \n");
-  if (!dR_) throw j_error("%s", no_R_msg_());
+  if (!dR_.get()) throw j_error("%s", no_R_msg_());
   SubbandDS* bf = bf_ptr_.operator->();
   const unsigned N = bf->chanN(), K = fftLen_ / 2 + 1;
   if (N != nChanR_) throw jdimension_error("The noise coherence matrix is %dx%d but there are %d channels\n", nChanR_, nChanR_, N);
@@ -2729,15 +2716,15 @@ void McCowanPostFilter::compute_(long from_frame)
   bf->effective_weights(w);
   bf->alignment_vector(!lef && (type_ & TYPE_ZELINSKI2) != 0, d);              // postfilter.cc:858-863 vs :1098
   const long Tn = T_ - from_frame;
-  const bool carry = carry_state_ && dPhi_ && dU_ && bf_version_ == bf->weights_version();
+  const bool carry = carry_state_ && dPhi_.get() && dU_.get() && bf_version_ == bf->weights_version();
   carry_state_ = false;
-  if (!dPhi_) { dPhi_ = dev_alloc(sizeof(float) * 2 * K); dPsi_ = dev_alloc(sizeof(float) * K); dWl_ = dev_alloc(sizeof(float) * K); }
-  if (!dU_) { dU_ = dev_alloc(sizeof(float) * 2 * K); dV_ = dev_alloc(sizeof(float) * 2 * K); }
+  if (!dPhi_.get()) { dPhi_.ensure(sizeof(float) * 2 * K); dPsi_.ensure(sizeof(float) * K); dWl_.ensure(sizeof(float) * K); }
+  if (!dU_.get()) { dU_.ensure(sizeof(float) * 2 * K); dV_.ensure(sizeof(float) * 2 * K); }
   if (!carry) {                                                                // (the next block of a stream continues the recursions)
-    dev_zero_async(dPhi_, sizeof(float) * 2 * K);
-    dev_zero_async(dPsi_, sizeof(float) * K);
-    dev_zero_async(dWl_, sizeof(float) * K);
-    dev_zero_async(dV_, sizeof(float) * 2 * K);
+    dev_zero_async(dPhi_.get(), sizeof(float) * 2 * K);
+    dev_zero_async(dPsi_.get(), sizeof(float) * K);
+    dev_zero_async(dWl_.get(), sizeof(float) * K);
+    dev_zero_async(dV_.get(), sizeof(float) * 2 * K);
   }
   void* dY = dYb_.ensure(sizeof(float) * 2 * K * (T_ ? T_ : 1));
   if (Tn > 0) {
@@ -2750,7 +2737,7 @@ void McCowanPostFilter::compute_(long from_frame)
     void* dCv = lef ? dCvb_.ensure(sizeof(float) * 2 * K * N * N) : NULL;
     h2d(dW, w.data(), sizeof(float) * w.size());
     h2d(dD, d.data(), sizeof(float) * d.size());
-    check_abi(btk_pf_coherence_coeffs(dR_, threshold_of_Rij_, (int)K, (int)N, dCs, dCv, nstream()));
+    check_abi(btk_pf_coherence_coeffs(dR_.get(), threshold_of_Rij_, (int)K, (int)N, dCs, dCv, nstream()));
     const float* Xo = static_cast<const float*>(dX) + 2 * from_frame;
     float* Yo = static_cast<float*>(dY) + 2 * from_frame;
     float* Uo = static_cast<float*>(dUs) + 2 * from_frame;
@@ -2764,36 +2751,33 @@ void McCowanPostFilter::compute_(long from_frame)
       if (svd_rule_ == "linpack_full" && (!lam_valid_ || lam_version_ != bf->weights_version() || lam_rule_ != svd_rule_)) {
         void* dLam = dLamb_.ensure(sizeof(float) * 2 * K);
         {                                                  // d^H A+ d from the reference's own inverse, every bin incl. 0 (:967-995)
-          void* fs = dev_alloc((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
-          check_abi(btk_mvdr_linpack_full(dR_, dD, NULL, dLam, (int)K, (int)N, 0, 0, 0, (float)minSV_, NULL, fs, nstream()));
+          DeviceBuffer fs((size_t)btk_mvdr_linpack_full_scratch_bytes((int)K, (int)N));
+          check_abi(btk_mvdr_linpack_full(dR_.get(), dD, NULL, dLam, (int)K, (int)N, 0, 0, 0, (float)minSV_, NULL, fs.get(), nstream()));
           nsync();
-          dev_free(fs);
           lam_valid_ = true; lam_version_ = bf->weights_version(); lam_rule_ = svd_rule_;
         }
       }
       if (!lam_valid_ || lam_version_ != bf->weights_version() || lam_rule_ != svd_rule_) {
         void* dLam = dLamb_.ensure(sizeof(float) * 2 * K);
-        void* dFb = dev_alloc(sizeof(int));
-        dev_zero_async(dFb, sizeof(int));
+        DeviceBuffer dFb(sizeof(int)), scratch;
+        dev_zero_async(dFb.get(), sizeof(int));
         const long sbytes = btk_mvdr_scratch_bytes((int)K, (int)N);
-        void* scratch = sbytes ? dev_alloc((size_t)sbytes) : NULL;
-        check_abi(btk_mvdr_lambda(dR_, dD, dLam, (int)K, (int)N, (float)minSV_, scratch, (int*)dFb, nstream()));
+        if (sbytes) scratch.ensure((size_t)sbytes);
+        check_abi(btk_mvdr_lambda(dR_.get(), dD, dLam, (int)K, (int)N, (float)minSV_, scratch.get(), (int*)dFb.get(), nstream()));
         if (svd_rule_ == "linpack") {                      // pseudoinverse() false -> identity, every bin incl. 0 (:971-977)
-          void* rs = dev_alloc((size_t)btk_mvdr_linpack_rule_scratch_bytes((int)K, (int)N));
-          check_abi(btk_mvdr_linpack_rule(dR_, dD, NULL, dLam, (int)K, (int)N, 0, 0, 0, (float)minSV_, NULL, NULL, rs, nstream()));
+          DeviceBuffer rs((size_t)btk_mvdr_linpack_rule_scratch_bytes((int)K, (int)N));
+          check_abi(btk_mvdr_linpack_rule(dR_.get(), dD, NULL, dLam, (int)K, (int)N, 0, 0, 0, (float)minSV_, NULL, NULL, rs.get(), nstream()));
           nsync();
-          dev_free(rs);
         }
         nsync();
-        dev_free(dFb); dev_free(scratch);
         lam_valid_ = true; lam_version_ = bf->weights_version(); lam_rule_ = svd_rule_;
       }
       invR_computed_ = true;
       check_abi(btk_lefkimmiatis_process(Yo, Uo, Vo, dLamb_.get(), (int)fbinX1_, 1, (int)K, (int)N, T_, Tn, alpha_, (int)type_,
-                                         min_frames_, base_ + from_frame, dPhi_, dV_, (float*)dWl_, nstream()));
+                                         min_frames_, base_ + from_frame, dPhi_.get(), dV_.get(), (float*)dWl_.get(), nstream()));
     } else {
       check_abi(btk_zelinski_process(Yo, Uo, Eo, 1, (int)K, (int)N, T_, Tn, alpha_, ((int)type_ & 15) | BTK_PF_MCCOWAN_RULES, min_frames_,
-                                     base_ + from_frame, dPhi_, (float*)dPsi_, (float*)dWl_, nstream()));
+                                     base_ + from_frame, dPhi_.get(), (float*)dPsi_.get(), (float*)dWl_.get(), nstream()));
     }
   }
   Yhost_valid_ = false;
@@ -2815,23 +2799,20 @@ LefkimmiatisPostFilter::LefkimmiatisPostFilter(VectorComplexFeatureStreamPtr& ou
 void LefkimmiatisPostFilter::calc_inverse_noise_spatial_spectral_matrix()
 {
   // calcLambda only needs d^H pinv(R) d, formed with the look direction when the block is computed
-  if (!dR_) throw j_error("%s", no_R_msg_());
+  if (!dR_.get()) throw j_error("%s", no_R_msg_());
   prepared_ = false; lam_valid_ = false;
 }
 
 // ================================================================================ SubbandGSCRLS
 SubbandGSCRLS::SubbandGSCRLS(unsigned fftLen, bool halfBandShift, float mu, float sigma2, const String& nm)
     : SubbandGSC(fftLen, halfBandShift, nm), mu_(mu), diagonal_weight_(sigma2), alpha_(-1.0f), qctype_(NO_QUADRATIC_CONSTRAINT),
-      rls_version_(0), is_wa_updated_(true), have_P_(false), dP_(NULL), dW_(NULL), dV_(NULL), dSS_(NULL), dCx_(NULL), dP0_(NULL),
-      dW0_(NULL), dSS0_(NULL), uploaded_version_(0), block_ran_(false) {}
-
-SubbandGSCRLS::~SubbandGSCRLS() { dev_free(dP_); dev_free(dW_); dev_free(dV_); dev_free(dSS_); dev_free(dCx_); dev_free(dP0_); dev_free(dW0_); dev_free(dSS0_); }
+      rls_version_(0), is_wa_updated_(true), have_P_(false), uploaded_version_(0), block_ran_(false) {}
 
 // quiescent weights and the further blocked directions as the kernels want them, from the weight object as it is NOW
 void SubbandGSCRLS::upload_weights_()
 {
   const unsigned N = chanN(), K = fftLen2_ + 1, NC = bfweight_->NC();
-  dev_free(dCx_); dCx_ = NULL;
+  dCx_.release();                                 // (NC may have changed: NULL without further directions, else a fresh block)
   if (NC > 1) {
     // the blocking matrix of calc_gsc_weights_2 / _n keeps N - NC columns: B B^H = I - conj(wq) wq^T / |wq|^2 - sum_j c_j c_j^H;
     // btk_nlms_constraint_vectors returns the directions of conj(B) B^T, i.e. the complex conjugates (include/btkhip.h)
@@ -2843,11 +2824,10 @@ void SubbandGSCRLS::upload_weights_()
                                             reinterpret_cast<double*>(&cx[(size_t)k * (NC - 1) * N])));
     }
     for (size_t i = 0; i < cx.size(); i++) cx[i] = std::conj(cx[i]);
-    dCx_ = dev_alloc(sizeof(double) * 2 * cx.size());
-    h2d(dCx_, cx.data(), sizeof(double) * 2 * cx.size());
+    h2d(dCx_.ensure(sizeof(double) * 2 * cx.size()), cx.data(), sizeof(double) * 2 * cx.size());
   }
-  if (!dV_) dV_ = dev_alloc(sizeof(double) * 2 * K * N);
-  h2d(dV_, bfweight_->wq_v.data(), sizeof(double) * 2 * K * N);                 // bins 0..M/2 of wq [M][N]
+  if (!dV_.get()) dV_.ensure(sizeof(double) * 2 * K * N);
+  h2d(dV_.get(), bfweight_->wq_v.data(), sizeof(double) * 2 * K * N);           // bins 0..M/2 of wq [M][N]
   wq_uploaded_.assign(bfweight_->wq_v.begin(), bfweight_->wq_v.begin() + (size_t)K * N);
   uploaded_version_ = weights_version_;
 }
@@ -2902,14 +2882,16 @@ void SubbandGSCRLS::alloc_state_()
 {
   if (!bfweight_) throw j_error("call calc_gsc_weights_x() once\n");
   const unsigned N = chanN(), K = fftLen2_ + 1;
-  dev_free(dP_); dev_free(dW_); dev_free(dV_); dV_ = NULL; dev_free(dSS_); dev_free(dP0_); dev_free(dW0_); dev_free(dSS0_);
-  dP_ = dev_alloc(sizeof(double) * 2 * K * N * N);
-  dW_ = dev_alloc(sizeof(double) * 2 * K * N);
-  dSS_ = dev_alloc(sizeof(double) * 4);
-  dP0_ = dev_alloc(sizeof(double) * 2 * K * N * N);
-  dW0_ = dev_alloc(sizeof(double) * 2 * K * N);
-  dSS0_ = dev_alloc(sizeof(double) * 4);
-  dev_zero_async(dSS_, sizeof(double) * 4);
+  // fresh blocks of exactly these sizes on every call: the channel count may have changed (upload_weights_ makes wq's anew)
+  const auto fresh = [](DeviceBuffer& b, size_t bytes) { b.release(); b.ensure(bytes); };
+  fresh(dP_, sizeof(double) * 2 * K * N * N);
+  fresh(dW_, sizeof(double) * 2 * K * N);
+  fresh(dSS_, sizeof(double) * 4);
+  fresh(dP0_, sizeof(double) * 2 * K * N * N);
+  fresh(dW0_, sizeof(double) * 2 * K * N);
+  fresh(dSS0_, sizeof(double) * 4);
+  dV_.release();
+  dev_zero_async(dSS_.get(), sizeof(double) * 4);
   upload_weights_();
 }
 
@@ -2918,9 +2900,9 @@ void SubbandGSCRLS::init_precision_matrix(float sigma2)
   alloc_state_();
   const unsigned N = chanN(), K = fftLen2_ + 1;
   const float p0 = 1 / sigma2;                                                // float division, beamformer.cc:1491
-  check_abi(btk_rls_init_nc(0, dV_, 0, dCx_, (int)bfweight_->NC(), (double)p0, 1, (int)K, (int)N, dP_, dW_, nstream()));
+  check_abi(btk_rls_init_nc(0, dV_.get(), 0, dCx_.get(), (int)bfweight_->NC(), (double)p0, 1, (int)K, (int)N, dP_.get(), dW_.get(), nstream()));
   // the active weights kept in the weight object are the starting point (zeros after calc_gsc_weights)
-  h2d(dW_, bfweight_->wl_v.data(), sizeof(double) * 2 * K * N);
+  h2d(dW_.get(), bfweight_->wl_v.data(), sizeof(double) * 2 * K * N);
   have_P_ = true;
   out_valid_ = false; Yhost_valid_ = false; block_ran_ = false;
 }
@@ -2930,8 +2912,8 @@ void SubbandGSCRLS::set_precision_matrix(unsigned fbinX, gsl_matrix_complex* Pz)
   if (!have_P_) {
     alloc_state_();
     const unsigned N = chanN(), K = fftLen2_ + 1;
-    dev_zero_async(dP_, sizeof(double) * 2 * K * N * N);
-    h2d(dW_, bfweight_->wl_v.data(), sizeof(double) * 2 * K * N);
+    dev_zero_async(dP_.get(), sizeof(double) * 2 * K * N * N);
+    h2d(dW_.get(), bfweight_->wl_v.data(), sizeof(double) * 2 * K * N);
     have_P_ = true;
   }
   const unsigned N = chanN(), bs = N - bfweight_->NC();
@@ -2955,7 +2937,7 @@ void SubbandGSCRLS::set_precision_matrix(unsigned fbinX, gsl_matrix_complex* Pz)
       for (unsigned j = 0; j < bs; j++) acc += T[(size_t)a * bs + j] * std::conj(B[(size_t)b * bs + j]);
       P[(size_t)a * N + b] = acc;
     }
-  h2d(static_cast<double*>(dP_) + (size_t)2 * fbinX * N * N, P.data(), sizeof(double) * 2 * N * N);
+  h2d(static_cast<double*>(dP_.get()) + (size_t)2 * fbinX * N * N, P.data(), sizeof(double) * 2 * N * N);
   out_valid_ = false; Yhost_valid_ = false; block_ran_ = false;
 }
 
@@ -2965,18 +2947,18 @@ void SubbandGSCRLS::run_block_()
 {
   const unsigned N = chanN(), K = fftLen2_ + 1;
   void* dX = snapshots_();
-  d2d_async(dP0_, dP_, sizeof(double) * 2 * K * N * N);
-  d2d_async(dW0_, dW_, sizeof(double) * 2 * K * N);
-  d2d_async(dSS0_, dSS_, sizeof(double) * 4);
+  d2d_async(dP0_.get(), dP_.get(), sizeof(double) * 2 * K * N * N);
+  d2d_async(dW0_.get(), dW_.get(), sizeof(double) * 2 * K * N);
+  d2d_async(dSS0_.get(), dSS_.get(), sizeof(double) * 4);
   void* dY = dYBuf_.ensure(sizeof(float) * 2 * K * (T_ ? T_ : 1));          // the block's output lives where the static apply's would
   const double params[6] = { (double)mu_, (double)diagonal_weight_, (double)(int)qctype_, (double)alpha_,
                              normalize_weight_ ? 1.0 : 0.0, is_wa_updated_ ? 1.0 : 0.0 };
   void* ws = dWs_.ensure((size_t)btk_rls_workspace_bytes(1, T_ ? T_ : 1));
-  check_abi(btk_rls_process_nc(0, params, dV_, 0, dCx_, (int)bfweight_->NC(), dX, dY, 1, (int)fftLen_, (int)N, T_, T_, dP_, dW_, (double*)dSS_, ws, nstream()));
+  check_abi(btk_rls_process_nc(0, params, dV_.get(), 0, dCx_.get(), (int)bfweight_->NC(), dX, dY, 1, (int)fftLen_, (int)N, T_, T_, dP_.get(), dW_.get(), (double*)dSS_.get(), ws, nstream()));
   out_valid_ = true; Yhost_valid_ = false;
   // export wl / wa of bins 1..M/2 as calcSidelobeCancellerU_f leaves them (beamformer.cc:1643)
   std::vector<cd> wl((size_t)K * N);
-  d2h(wl.data(), dW_, sizeof(double) * 2 * K * N);
+  d2h(wl.data(), dW_.get(), sizeof(double) * 2 * K * N);
   const unsigned bs = N - bfweight_->NC();
   for (unsigned k = 1; k < K; k++) {
     const cd* B = &bfweight_->B_v[(size_t)k * N * bs];
@@ -3043,13 +3025,13 @@ void SubbandGSCRLS::refresh_block_()
     if (kept_frames(frame_no_, handed_, chunk_base_, T_) > 0)
       throw jconsistency_error("SubbandGSCRLS: the weights changed after frames of this block were served; reset() first\n");
     const unsigned N = chanN(), K = fftLen2_ + 1;
-    d2d_async(dP_, dP0_, sizeof(double) * 2 * K * N * N);
-    d2d_async(dW_, dW0_, sizeof(double) * 2 * K * N);
-    d2d_async(dSS_, dSS0_, sizeof(double) * 4);
+    d2d_async(dP_.get(), dP0_.get(), sizeof(double) * 2 * K * N * N);
+    d2d_async(dW_.get(), dW0_.get(), sizeof(double) * 2 * K * N);
+    d2d_async(dSS_.get(), dSS0_.get(), sizeof(double) * 4);
   }
   if (uploaded_version_ != weights_version_) {
     const bool had_state = !wq_uploaded_.empty();
-    if (had_state) change_basis_(dP_, dW_);                 // (uses the wq the state was built with, then ...)
+    if (had_state) change_basis_(dP_.get(), dW_.get());     // (uses the wq the state was built with, then ...)
     upload_weights_();                                      // ... the new wq / blocked directions go to the device
   }
   run_block_();
@@ -3308,7 +3290,7 @@ MultiChannelWPEDereverberation::MultiChannelWPEDereverberation(unsigned subbands
                                                                double bandWidth, double diagonal_bias, double sampleRate)
     : subbandsN_(subbandsN), channelsN_(channelsN), lowerN_(lowerN), upperN_(upperN), iterationsN_(iterationsN),
       load_db_(loadDb), diagonal_bias_(diagonal_bias), lower_bw_(wpe_band_width(subbandsN, bandWidth, sampleRate)),
-      upper_bw_(subbandsN - lower_bw_), estimated_(false), framesN_(0), dG_(NULL), T_(0), have_out_(false),
+      upper_bw_(subbandsN - lower_bw_), estimated_(false), framesN_(0), T_(0), have_out_(false),
       output_(new gsl_vector_complex*[channelsN]), frame_no_(-1)
 {
   for (unsigned c = 0; c < channelsN_; c++) output_[c] = gsl_vector_complex_calloc(subbandsN_);
@@ -3318,7 +3300,6 @@ MultiChannelWPEDereverberation::~MultiChannelWPEDereverberation()
 {
   for (unsigned c = 0; c < channelsN_; c++) gsl_vector_complex_free(output_[c]);
   delete[] output_;
-  dev_free(dG_);
 }
 
 void MultiChannelWPEDereverberation::set_input(VectorComplexFeatureStreamPtr& samples)
@@ -3340,13 +3321,13 @@ void MultiChannelWPEDereverberation::reset_filter() { estimated_ = false; frames
 void MultiChannelWPEDereverberation::next_speaker()
 {
   reset();
-  if (dG_) {
+  if (dG_.get()) {
     const unsigned K = subbandsN_ / 2 + 1, P = channelsN_ * (upperN_ - lowerN_ + 1);
-    dev_zero_async(dG_, sizeof(float) * 2 * channelsN_ * K * P);
+    dev_zero_async(dG_.get(), sizeof(float) * 2 * channelsN_ * K * P);
   }
 }
 
-long MultiChannelWPEDereverberation::snapshots_(void** dX)
+long MultiChannelWPEDereverberation::snapshots_(DeviceBuffer& dX)
 {
   const unsigned C = channelsN_, K = subbandsN_ / 2 + 1;
   if (sources_.size() != C) throw jallocation_error("%u of %u input channels are set\n", (unsigned)sources_.size(), C);
@@ -3363,8 +3344,8 @@ long MultiChannelWPEDereverberation::snapshots_(void** dX)
         Xh[2 * (((size_t)k * C + c) * T + t)] = fr[c][2 * ((size_t)t * K + k)];
         Xh[2 * (((size_t)k * C + c) * T + t) + 1] = fr[c][2 * ((size_t)t * K + k) + 1];
       }
-  *dX = dev_alloc(sizeof(float) * Xh.size());
-  if (!Xh.empty()) h2d(*dX, Xh.data(), sizeof(float) * Xh.size());
+  dX.ensure(sizeof(float) * Xh.size());
+  if (!Xh.empty()) h2d(dX.get(), Xh.data(), sizeof(float) * Xh.size());
   return T;
 }
 
@@ -3373,32 +3354,24 @@ long MultiChannelWPEDereverberation::snapshots_(void** dX)
 unsigned MultiChannelWPEDereverberation::estimate_filter(int start_frame_no, int end_frame_no)
 {
   const unsigned C = channelsN_, K = subbandsN_ / 2 + 1, P = C * (upperN_ - lowerN_ + 1);
-  void* dX = NULL;
-  const long T = snapshots_(&dX);
+  DeviceBuffer dX;
+  const long T = snapshots_(dX);
   long n = T;
   if (end_frame_no >= 0) {
     n = (long)end_frame_no - (start_frame_no > 0 ? start_frame_no : 0);
     n = n < 0 ? 0 : (n > T ? T : n);
   }
-  if (!dG_) {
-    dG_ = dev_alloc(sizeof(float) * 2 * C * K * P);
-    dev_zero_async(dG_, sizeof(float) * 2 * C * K * P);
+  if (!dG_.get()) {
+    dev_zero_async(dG_.ensure(sizeof(float) * 2 * C * K * P), sizeof(float) * 2 * C * K * P);
   }
   const long wsb = btk_wpe_workspace_bytes(1, (int)K, (int)C, (int)lowerN_, (int)upperN_, T > 0 ? T : 1);
-  void* ws = dev_alloc((size_t)(wsb > 0 ? wsb : 16));
-  void* dfail = dev_alloc(sizeof(int));
-  dev_zero_async(dfail, sizeof(int));
+  DeviceBuffer ws((size_t)(wsb > 0 ? wsb : 16)), dfail(sizeof(int));
+  dev_zero_async(dfail.get(), sizeof(int));
   int fail = 0;
-  try {
-    check_abi(btk_wpe_estimate(dX, 1, (int)K, (int)C, T > 0 ? T : 1, n, (int)lowerN_, (int)upperN_, (int)iterationsN_, load_db_,
-                               diagonal_bias_, (int)lower_bw_, (int)upper_bw_, dG_, ws, (int*)dfail, nstream()));
-    nsync();
-    d2h(&fail, dfail, sizeof(int));
-  } catch (...) {
-    dev_free(dX); dev_free(ws); dev_free(dfail);
-    throw;
-  }
-  dev_free(dX); dev_free(ws); dev_free(dfail);
+  check_abi(btk_wpe_estimate(dX.get(), 1, (int)K, (int)C, T > 0 ? T : 1, n, (int)lowerN_, (int)upperN_, (int)iterationsN_, load_db_,
+                             diagonal_bias_, (int)lower_bw_, (int)upper_bw_, dG_.get(), ws.get(), (int*)dfail.get(), nstream()));
+  nsync();
+  d2h(&fail, dfail.get(), sizeof(int));
   if (fail > 0)
     throw jnumeric_error("MultiChannelWPEDereverberation: Cholesky decomposition failed (%d systems).\n"
                          "Some channels may be too similar. Try to increase 'diagonal_bias'", fail);
@@ -3413,19 +3386,15 @@ unsigned MultiChannelWPEDereverberation::estimate_filter(int start_frame_no, int
 void MultiChannelWPEDereverberation::prepare_output_()
 {
   const unsigned C = channelsN_, K = subbandsN_ / 2 + 1;
-  void* dX = NULL;
-  T_ = snapshots_(&dX);
+  DeviceBuffer dX;
+  T_ = snapshots_(dX);
   out_.assign((size_t)2 * K * C * (T_ > 0 ? T_ : 0), 0.f);
   if (T_ > 0) {
-    void* dO = dev_alloc(sizeof(float) * out_.size());
-    try {
-      check_abi(btk_wpe_apply(dX, dG_, dO, 1, (int)K, (int)C, T_, T_, (int)lowerN_, (int)upperN_, (int)lower_bw_, (int)upper_bw_, nstream()));
-      nsync();
-      d2h(out_.data(), dO, sizeof(float) * out_.size());
-    } catch (...) { dev_free(dX); dev_free(dO); throw; }
-    dev_free(dO);
+    DeviceBuffer dO(sizeof(float) * out_.size());
+    check_abi(btk_wpe_apply(dX.get(), dG_.get(), dO.get(), 1, (int)K, (int)C, T_, T_, (int)lowerN_, (int)upperN_, (int)lower_bw_, (int)upper_bw_, nstream()));
+    nsync();
+    d2h(out_.data(), dO.get(), sizeof(float) * out_.size());
   }
-  dev_free(dX);
   have_out_ = true;
 }
 

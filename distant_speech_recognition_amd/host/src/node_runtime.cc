@@ -36,6 +36,7 @@ void check_hip(hipError_t e, const char* what)
 std::atomic<long> g_device_allocs(0), g_pinned_allocs(0);
 std::atomic<long long> g_pull_ns(0), g_upload_ns(0), g_device_ns(0);
 static std::atomic<long long> g_d2h_bytes(0);
+static std::atomic<long> g_live_device_blocks(0);
 
 hipStream_t nstream() { return static_cast<hipStream_t>(btk_node_stream()); }
 static thread_local hipStream_t t_cstream = NULL;
@@ -47,14 +48,6 @@ hipStream_t cstream()
 void csync_if_open() { if (t_cstream) (void)hipStreamSynchronize(t_cstream); }
 void nsync() { check_hip(hipStreamSynchronize(nstream()), "hipStreamSynchronize"); }
 
-void* dev_alloc(size_t bytes)
-{
-  void* p = NULL;
-  check_hip(hipMalloc(&p, bytes ? bytes : 16), "hipMalloc");
-  g_device_allocs++;
-  return p;
-}
-void dev_free(void* p) { if (p) (void)hipFree(p); }
 void h2d(void* d, const void* h, size_t n)
 {
   if (!n) return;
@@ -139,6 +132,7 @@ void btk_node_alloc_counts(long* device_allocs, long* pinned_allocs)
   if (device_allocs) *device_allocs = g_device_allocs.load();
   if (pinned_allocs) *pinned_allocs = g_pinned_allocs.load();
 }
+long btk_node_live_device_blocks() { return g_live_device_blocks.load(); }
 
 long long btk_node_d2h_bytes() { return g_d2h_bytes.load(std::memory_order_relaxed); }
 void btk_node_d2h_bytes_reset() { g_d2h_bytes.store(0, std::memory_order_relaxed); }
@@ -156,13 +150,17 @@ void* DeviceBuffer::ensure(size_t bytes)
 {
   if (bytes <= cap_ && p_) return p_;
   const size_t want = std::max(bytes ? bytes : (size_t)16, cap_ + cap_ / 2);
-  if (p_) { nsync(); (void)hipFree(p_); p_ = NULL; cap_ = 0; }          // launches that still read the old block
+  if (p_) { nsync(); release(); }                                         // launches that still read the old block
   check_hip(hipMalloc(&p_, want), "hipMalloc");
-  g_device_allocs++;
+  g_device_allocs++; g_live_device_blocks++;
   cap_ = want;
   return p_;
 }
-void DeviceBuffer::release() { if (p_) (void)hipFree(p_); p_ = NULL; cap_ = 0; }
+void DeviceBuffer::release()
+{
+  if (p_) { (void)hipFree(p_); g_live_device_blocks--; }
+  p_ = NULL; cap_ = 0;
+}
 
 void* PinnedBuffer::ensure(size_t bytes) { return ensure_keep(bytes, 0); }
 void* PinnedBuffer::ensure_keep(size_t bytes, size_t keep_bytes)

@@ -29,10 +29,8 @@ hipStream_t cstream();
 void csync_if_open();
 void nsync();
 
-// one-off device blocks of the design-time paths (weight design, WPE estimate, CSD rebuild): not the per-block steady state.
-// Counted into btk_node_alloc_counts().
-void* dev_alloc(size_t bytes);
-void dev_free(void* p);
+// (device and pinned memory: DeviceBuffer / PinnedBuffer of common/devmem.h, members for a node's state and locals for the
+// one-off blocks of the design-time paths -- nothing else in the node layer allocates or frees)
 // copies between pageable host memory and the device, complete on return, ordered on the node stream like every launch
 void h2d(void* d, const void* h, size_t n);
 void d2h(void* h, const void* d, size_t n);

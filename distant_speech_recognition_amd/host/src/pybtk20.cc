@@ -872,7 +872,8 @@ PYBIND11_MODULE(_btk20cpp, m)
              }
              return out; });
   m.def("node_synchronize", []() { btk_node_synchronize(); });     // wait for everything this thread's nodes have launched
-  m.def("node_alloc_counts", []() { long d = 0, h = 0; btk_node_alloc_counts(&d, &h); return py::make_tuple(d, h); });   // (hipMalloc, hipHostMalloc) calls so far
+  m.def("node_alloc_counts", []() { long d = 0, h = 0; btk_node_alloc_counts(&d, &h); return py::make_tuple(d, h); });   // (device, pinned) allocation calls so far
+  m.def("node_live_device_blocks", []() { return btk_node_live_device_blocks(); });   // device blocks the nodes hold right now
   m.def("node_d2h_bytes", []() { return btk_node_d2h_bytes(); });              // bytes copied device -> host by the nodes since the last reset
   m.def("node_d2h_bytes_reset", []() { btk_node_d2h_bytes_reset(); });
 

@@ -14,12 +14,14 @@
 namespace {
 
 using btknode::check_abi;
-using btknode::check_hip;
 using btknode::nstream;
 using btknode::d2h;
 using btknode::h2d;
 using btknode::even_pitch;
 using btknode::d2d_async;
+using btknode::d2d_2d_async;
+using btknode::h2d_async;
+using btknode::dev_zero_async;
 
 }  // namespace
 
@@ -33,11 +35,6 @@ EnhancementBlockNode_::EnhancementBlockNode_(unsigned fftLen, bool channel_major
     throw jdimension_error("%s: %d subbands are outside this engine's enhancement nodes (even, at most 2048)\n", nm.c_str(), (int)fftLen_);
 }
 
-EnhancementBlockNode_::~EnhancementBlockNode_()
-{
-  for (size_t i = 0; i < dPcm_.size(); i++) delete dPcm_[i];
-}
-
 void EnhancementBlockNode_::add_source_(const VectorComplexFeatureStreamPtr& s)
 {
   if (s->size() != fftLen_)
@@ -46,7 +43,7 @@ void EnhancementBlockNode_::add_source_(const VectorComplexFeatureStreamPtr& s)
   if ((int)srcs_.size() >= btk_ss_max_channels())
     throw jdimension_error("%s: more than %d channels\n", name().c_str(), btk_ss_max_channels());
   srcs_.push_back(s);
-  dPcm_.push_back(new DeviceBuffer());
+  dPcm_.push_back(std::unique_ptr<DeviceBuffer>(new DeviceBuffer()));
   banks_.clear();
   for (size_t i = 0; i < srcs_.size(); i++) {
     OverSampledDFTAnalysisBank* b = dynamic_cast<OverSampledDFTAnalysisBank*>(srcs_[i].operator->());
@@ -113,7 +110,7 @@ bool EnhancementBlockNode_::gather_banks_(long f0, long& Tn)
                                name().c_str(), b->name().c_str());
     const long L = (b->blocks_pulled() - b0) * D;               // (samples past the end of an ended source read as zeros)
     float* dp = static_cast<float*>(dPcm_[i]->ensure(sizeof(float) * (L > 0 ? L : 1)));
-    if (L > 0) check_hip(hipMemcpyAsync(dp, b->window(b0), sizeof(float) * L, hipMemcpyHostToDevice, nstream()), "hipMemcpyAsync H2D");
+    if (L > 0) h2d_async(dp, b->window(b0), sizeof(float) * L);
     if (C == 1) {
       check_abi(btk_fb_analysis(b->plan(), dp, L > 0 ? L : 0, L > 0 ? L : 1, 1, 1, dx, Ts, f0 - b0, Tn, nstream()));
     } else {
@@ -121,8 +118,7 @@ bool EnhancementBlockNode_::gather_banks_(long f0, long& Tn)
       check_abi(btk_fb_analysis(b->plan(), dp, L > 0 ? L : 0, L > 0 ? L : 1, 1, 1, dc, Ts, f0 - b0, Tn, nstream()));
       const size_t row = sizeof(float) * 2 * Ts;
       char* dst = channel_major_ ? dx + i * K * row : dx + i * row;
-      check_hip(hipMemcpy2DAsync(dst, channel_major_ ? row : C * row, dc, row, sizeof(float) * 2 * Tn, K, hipMemcpyDeviceToDevice,
-                                 nstream()), "hipMemcpy2DAsync D2D");
+      d2d_2d_async(dst, channel_major_ ? row : C * row, dc, row, sizeof(float) * 2 * Tn, K);
     }
   }
   btk_node_synchronize();                                       // the windows move when the banks release what is done
@@ -183,8 +179,7 @@ void EnhancementBlockNode_::copy_source_blocks_(long T)
     if (!p || Ti != T)
       throw jconsistency_error("%s: source %d changed the length of its block (%ld -> %ld frames)\n", name().c_str(), (int)i, T, Ti);
     char* dst = channel_major_ ? dx + i * K * row : dx + i * row;
-    check_hip(hipMemcpy2DAsync(dst, channel_major_ ? row : C * row, p, sizeof(float) * 2 * Tsi, sizeof(float) * 2 * T, K,
-                               hipMemcpyDeviceToDevice, nstream()), "hipMemcpy2DAsync D2D");
+    d2d_2d_async(dst, channel_major_ ? row : C * row, p, sizeof(float) * 2 * Tsi, sizeof(float) * 2 * T, K);
     src_versions_[i] = bsrcs_[i]->block_version();
   }
 }
@@ -504,7 +499,7 @@ unsigned char* SpectralSubtractor::added_(void* st) const { return reinterpret_c
 
 void SpectralSubtractor::init_state_(void* d)
 {
-  check_hip(hipMemsetAsync(d, 0, state_bytes_(), nstream()), "hipMemsetAsync");
+  dev_zero_async(d, state_bytes_());
 }
 
 void SpectralSubtractor::launch_(const void* dX, void* dOut, long Ts, long t0, long t1, long frames_done)
@@ -601,7 +596,7 @@ WienerFilter::WienerFilter(VectorComplexFeatureStreamPtr& targetSignal, VectorCo
 }
 
 size_t WienerFilter::state_bytes_() const { return sizeof(double) * 2 * (fftLen_ / 2 + 1); }      // psd_s [K] | psd_n [K]
-void WienerFilter::init_state_(void* d) { check_hip(hipMemsetAsync(d, 0, state_bytes_(), nstream()), "hipMemsetAsync"); }
+void WienerFilter::init_state_(void* d) { dev_zero_async(d, state_bytes_()); }
 
 void WienerFilter::launch_(const void* dX, void* dOut, long Ts, long t0, long t1, long frames_done)
 {
